@@ -7,19 +7,28 @@ nprobe=32, k=10, ONE batch of 10 000 queries.  One "step" = one search() of that
 batch with queries and results resident in HBM.  N > 1: index replicated on every
 GPU, the batch split ceil(nq/N) per rank (IndexProxy.cpp:139-149), one RCCL
 all-gather of the per-rank top-k rows per step = strong scaling (the north star's
-mode); the weak-scaling figure (10 000 queries per GPU) is measured in the same run
-and reported as "other_scaling".
+mode); with --full the weak-scaling figure (10 000 queries per GPU) is measured in the
+same run and reported as "other_scaling".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 `python bench.py --gpus N` without a launcher starts the N ranks itself (fresh child
-processes, before this process touches the GPU).  A rank count / device / gather
-mismatch exits non-zero.
+processes, before this process touches the GPU).  A rank count / device mismatch exits
+non-zero.
+
+A plain run does only what the headline needs: set-up, the untimed pre-warm, --warmup
+steps, --steps timed steps and the result line.  --full adds everything else: HIP
+events in the timed region (roofline, stage_ms), the cold-path calls, the
+asserted all-gather check and the other scaling mode (N > 1), the parity spot check,
+recall, host buffers, the other data set, float16 tables, the VLQ / multi-index /
+Deep1B-shape legs and the CPU baseline.  --dump-outputs DIR writes the last timed
+step's results as DIR/distances.npy (float32) and DIR/labels.npy (float64); the inputs
+are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).  torch is used for device memory, streams,
 synthetic data/training set-up and torch.distributed; the timed region is the
 HIP library behind include/vlq_ivfpq.h only.  The oracle (oracle/) is used for
-the cpu_baseline leg and a parity spot check, never in the timed region.
+the cpu_baseline leg and a parity spot check (--full), never in the timed region.
 """
 import argparse
 import json
@@ -62,7 +71,18 @@ def gmm(torch, gen, centres, n, sigma, dev, rank=0, spread=0.0):
 
 
 def kmeans(torch, x, k, niter, gen):
-    """Plain Lloyd (set-up only; training is outside the hot path)."""
+    """Plain Lloyd (set-up only; training is outside the hot path).  The cluster sums take torch's
+    deterministic index_add_ (sorted, not float atomics), so the same seeds train the same quantizers in every run and
+    --dump-outputs of two runs can be compared bit for bit."""
+    was = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        return _lloyd(torch, x, k, niter, gen)
+    finally:
+        torch.use_deterministic_algorithms(was[0], warn_only=was[1])
+
+
+def _lloyd(torch, x, k, niter, gen):
     n = x.shape[0]
     cent = x[torch.randperm(n, generator=gen, device=x.device)[:k]].clone()
     for _ in range(niter):
@@ -81,7 +101,7 @@ def kmeans(torch, x, k, niter, gen):
 def build_index(args, dev, xt=None, xb=None, bcast=None):
     """xt / xb given: real vectors (.fvecs); otherwise generator G1 of SURVEY.md section 8(d).
     bcast(t): N > 1 -- the quantizers are trained on rank 0 and broadcast, so that every rank holds the SAME
-    index (the k-means below accumulates with float atomics: two GPUs would not train bit-equal centroids)."""
+    index (one training, whatever the devices' arithmetic)."""
     import torch
     import vector_line_quantization_amd as vlq
     d, nlist, M, nbits = args.d, args.nlist, args.M, 8
@@ -591,6 +611,20 @@ def deep1b_c4_leg(torch, dev, per_list=4096, nq=10000, reps=3, nsample=64):
 
 
 TIMED_PROFILE = 3
+DUMP_BYTES = (64 << 20) - 4096      # --dump-outputs budget, room left for the .npy headers
+
+
+def dump_outputs(path, D, I):
+    """--dump-outputs: the rows the timed path returned in its last step, distances as float32 and labels as float64
+    (exact below 2^53).  Past the budget, a fixed seeded sample of the rows, their indices in rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n, k = D.shape
+    if n * 12 * k > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (12 * k + 8), replace=False))
+        D, I = D[rows], I[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), np.ascontiguousarray(D, dtype=np.float32))
+    np.save(os.path.join(path, "labels.npy"), np.ascontiguousarray(I, dtype=np.float64))
 
 
 def main():
@@ -632,7 +666,14 @@ def main():
     ap.add_argument("--no-imi", action="store_true", help="skip the multi-index (configs[2] / SURVEY C3 geometry) leg")
     ap.add_argument("--no-deep1b", action="store_true", help="skip the Deep1B-shape (configs[3] / SURVEY C4 geometry) leg")
     ap.add_argument("--cpu-queries", type=int, default=10000)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: instrumented timed region (roofline, stage_ms), cold path, gather "
+                         "check and other scaling mode, parity, recall, host buffers, the other legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's distances (float32) and labels (float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     defaults = {k: ap.get_default(k) for k in ("nq", "nb", "nt", "d", "nlist", "M", "nprobe", "k", "sigma",
                                                "gmm_centres", "rank", "spread")}
     default_workload = all(getattr(args, k) == v for k, v in defaults.items())
@@ -700,7 +741,6 @@ def main():
     gt = None
     if stub:
         g, centres, coarse, pq, xb = StubIndex(), None, None, None, None
-        imb = 0.0
     elif fdir:
         xt_h, xb_h, xq_h0 = (fvecs_read(os.path.join(fdir, f)) for f in ("learn.fvecs", "base.fvecs", "query.fvecs"))
         args.d, args.nt, args.nb, args.nq = xb_h.shape[1], xt_h.shape[0], xb_h.shape[0], xq_h0.shape[0]
@@ -709,10 +749,8 @@ def main():
             gt = fvecs_read(gpath).view(np.int32)[:, 0].astype(np.int64)
         g, centres, coarse, pq, xb = build_index(args, dev, xt=torch.from_numpy(xt_h).to(dev), xb=torch.from_numpy(xb_h).to(dev), bcast=bcast)
         default_workload = False
-        lens, imb = list_stats(g, args.nlist)
     else:
         g, centres, coarse, pq, xb = build_index(args, dev, bcast=bcast)
-        lens, imb = list_stats(g, args.nlist)
 
     def queries(seed, n):
         if stub:
@@ -729,10 +767,11 @@ def main():
     prewarm = [0]
     cold = {}
 
-    def run_mode(mode, steps, warmup, instrument):
+    def run_mode(mode, steps, warmup, instrument, full, dump):
         """One timed region in `mode`.  strong: every rank holds the SAME batch of nq queries and searches
         its ceil(nq/world) slice; weak: nq queries of its own per rank.  Per step: search the slice, then
-        ONE all-gather of the packed (D | I) rows of the slice -- the per-shard top-k to every rank."""
+        ONE all-gather of the packed (D | I) rows of the slice -- the per-shard top-k to every rank.
+        full: also the cold-path calls and the asserted gather check; dump: keep the last timed step's rows."""
         if mode == "strong":
             xq_full = queries(33, args.nq)
             lo, hi, per = shard_bounds(args.nq, world, rank)
@@ -759,6 +798,11 @@ def main():
                     pend[b].wait()
                     pend[b] = None
 
+        def gathered(b):
+            gb = gath[b].view(world, slot)
+            return (torch.cat([gb[r, :per * k * 4].view(torch.float32).view(per, k) for r in range(world)]),
+                    torch.cat([gb[r, nbytes_d:].view(torch.int64).view(per, k) for r in range(world)]))
+
         def step():
             b = nstep[0] & 1
             nstep[0] += 1
@@ -770,7 +814,7 @@ def main():
             if use_dist:   # per-shard top-k -> every rank (north star: RCCL all-gather over xGMI)
                 pend[b] = dist.all_gather_into_tensor(gath[b], pack[b], async_op=True)
 
-        if not stub and "first_call_ms" not in cold and ns > 0:
+        if full and not stub and "first_call_ms" not in cold and ns > 0:
             # What a driver that calls search ONCE gets (untimed here, labelled): the first search of the fresh handle in this
             # fresh process -- it builds the precomputed table (IndexIVFPQ::precompute_table: the reference does that at
             # train / read_index time), grows the workspace, and runs with no measured walk period and cold clocks -- and the
@@ -826,6 +870,18 @@ def main():
             dist.barrier()
         sync()
         elapsed = time.perf_counter() - t0
+        outputs = None
+        if dump:
+            # what the caller of the timed path holds after its last step: the all-gathered rows of the batch when
+            # the ranks exchange them, the rank's own rows otherwise
+            b = (nstep[0] - 1) & 1
+            if use_dist:
+                Dl, Il = gathered(b)
+                nrow = args.nq if mode == "strong" else world * per
+                Dl, Il = Dl[:nrow], Il[:nrow]
+            else:
+                Dl, Il = Ds[b][:ns], Is[b][:ns]
+            outputs = (Dl.cpu().numpy().copy(), Il.cpu().numpy().copy())
         prof = g.profile_read(reset=True) if instrument else None
         _nq_stat, ncode = g.stats(reset=True)
         prof_all = None
@@ -862,15 +918,15 @@ def main():
                 cold["scan_info"] = g.last_scan_info()
                 g.stats(reset=True)
         b = (nstep[0] - 1) & 1
+        gather_ok = None
         if use_dist:
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if use_dist and full:
             # ASSERTED: the gathered rows are what a single index returns for the same queries.  strong: rank
             # 0's own search of the WHOLE batch; weak: every rank's slot is its own result.
-            gb = gath[b].view(world, slot)
-            Dall = torch.cat([gb[r, :per * k * 4].view(torch.float32).view(per, k) for r in range(world)])
-            Iall = torch.cat([gb[r, nbytes_d:].view(torch.int64).view(per, k) for r in range(world)])
+            Dall, Iall = gathered(b)
             if mode == "strong":
                 Dchk = torch.empty((args.nq, k), dtype=torch.float32, device=dev)
                 Ichk = torch.empty((args.nq, k), dtype=torch.int64, device=dev)
@@ -887,19 +943,18 @@ def main():
                 raise SystemExit("bench.py: all-gathered results differ from the single-index results (%s scaling)" % mode)
             gather_ok = True
             g.stats(reset=True)
-        else:
-            gather_ok = None
         total_q = (args.nq if mode == "strong" else world * args.nq) * steps
         return {"elapsed": elapsed, "qps": total_q / elapsed, "ms_per_step": elapsed / steps * 1e3, "prof": prof,
                 "prof_all": prof_all, "ncode": ncode, "gather_ok": gather_ok, "xq": xs, "D": Ds[b][:ns], "I": Is[b][:ns],
-                "queries_per_rank": ns}
+                "queries_per_rank": ns, "outputs": outputs}
 
     main_mode = args.scaling if world > 1 else "strong"
-    res = run_mode(main_mode, args.steps, args.warmup, instrument=not stub)
+    res = run_mode(main_mode, args.steps, args.warmup, instrument=args.full and not stub, full=args.full,
+                   dump=bool(args.dump_outputs) and rank == 0)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         other_mode = "weak" if main_mode == "strong" else "strong"
-        other = run_mode(other_mode, args.steps, args.warmup, instrument=False)
+        other = run_mode(other_mode, args.steps, args.warmup, instrument=False, full=True, dump=False)
         other["mode"] = other_mode
     elapsed, prof, prof_all, ncode, gather_ok = res["elapsed"], res["prof"], res["prof_all"], res["ncode"], res["gather_ok"]
     xq, D, I = res["xq"], res["D"], res["I"]
@@ -910,6 +965,15 @@ def main():
             dist.destroy_process_group()
         return
 
+    if res["outputs"] is not None:
+        dump_outputs(args.dump_outputs, *res["outputs"])
+
+    def finish(out):
+        print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
     if stub:
         out = {"stub": True, "metric": "launcher/sharding self-test (no measurement)", "value": res["qps"], "unit": "queries/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
@@ -917,15 +981,33 @@ def main():
                "queries_per_rank": res["queries_per_rank"]}}
         if other is not None:
             out["other_scaling"] = {"scaling": other["mode"], "value": other["qps"], "all_gather_check": other["gather_ok"]}
-        print(json.dumps(out), flush=True)
-        if use_dist:
-            dist.barrier()
-            dist.destroy_process_group()
+        finish(out)
         return
 
     steps = args.steps
     qps = res["qps"]
     nq_rank = res["queries_per_rank"]
+    out = {
+        "metric": "queries/sec @ recall@1 (SIFT1M, nlist=4096 m=16 nprobe=32 k=10)",
+        "value": qps, "unit": "queries/s", "n_gpus": world, "steps": steps, "warmup": args.warmup, "prewarm_steps": prewarm[0],
+        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": main_mode,
+        "vs_baseline": None, "dtype": "f32",
+        "data": ("SIFT1M .fvecs from %s" % fdir) if fdir else
+                ("synthetic (SIFT1M-shaped GMM bytes, generator flags --sigma %g --rank %d --spread %g; no dataset on the box)"
+                 % (args.sigma, args.rank, args.spread)),
+        "rccl_ranks": rccl_ranks,
+        "config": {"workload": "configs[1]: %s, d=%d nb=%d nlist=%d M=%dx8bit "
+                               "nprobe=%d k=%d, %s, precomputed-table mode 1"
+                               % ("SIFT1M .fvecs" if fdir else "SIFT1M-shaped GMM bytes", args.d, args.nb, args.nlist,
+                                  args.M, args.nprobe, args.k,
+                                  ("ONE batch of %d queries split %d per GPU (strong scaling)" % (args.nq, nq_rank))
+                                  if main_mode == "strong" else ("%d queries per GPU (weak scaling)" % args.nq)),
+                   "parallelism": "index replicated, queries sharded x%d, one RCCL all-gather of the packed top-k rows per step" % world},
+    }
+    if not args.full:
+        finish(out)
+        return
+
     # scan launches per step from the five fully instrumented steps (the timed region times a sample of its launches)
     launches_per_step = max(1, prof_all["scan_calls"] // 5)
     ncode_per_launch = ncode / max(1, steps * launches_per_step)
@@ -957,46 +1039,30 @@ def main():
         except Exception:
             traffic = None
 
-    out = {
-        "metric": "queries/sec @ recall@1 (SIFT1M, nlist=4096 m=16 nprobe=32 k=10)",
-        "value": qps, "unit": "queries/s", "n_gpus": world, "steps": steps, "warmup": args.warmup, "prewarm_steps": prewarm[0],
-        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": main_mode,
-        "vs_baseline": None, "dtype": "f32",
-        "data": ("SIFT1M .fvecs from %s" % fdir) if fdir else
-                ("synthetic (SIFT1M-shaped GMM bytes, generator flags --sigma %g --rank %d --spread %g; no dataset on the box)"
-                 % (args.sigma, args.rank, args.spread)),
-        "rccl_ranks": rccl_ranks,
-        "config": {"workload": "configs[1]: %s, d=%d nb=%d nlist=%d M=%dx8bit "
-                               "nprobe=%d k=%d, %s, precomputed-table mode 1"
-                               % ("SIFT1M .fvecs" if fdir else "SIFT1M-shaped GMM bytes", args.d, args.nb, args.nlist,
-                                  args.M, args.nprobe, args.k,
-                                  ("ONE batch of %d queries split %d per GPU (strong scaling)" % (args.nq, nq_rank))
-                                  if main_mode == "strong" else ("%d queries per GPU (weak scaling)" % args.nq)),
-                   "parallelism": "index replicated, queries sharded x%d, one RCCL all-gather of the packed top-k rows per step" % world,
-                   "list_imbalance": round(imb, 3), "ncode_per_query": ncode_per_launch / max(1, nq_rank)},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                     "kernel": "vlq::scan16_kernel", "kernel_ms": scan_ms,
-                     # `achieved` / `frac` are ALGORITHMIC code bytes over kernel time: an effective rate,
-                     # part of it served by L2 / Infinity Cache.  frac_measured = bytes the fabric counters saw over the
-                     # same time (null when no counter run matches this build and workload).
-                     "frac_measured": (traffic / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and scan_ms > 0) else None,
-                     "algorithmic_bytes": code_bytes,
-                     "lut_bytes_separate": lut_bytes,
-                     "lut_plus_code_GBps": (code_bytes + lut_bytes) / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0,
-                     # the kernel's other resource: one random 32-bit LDS gather per code byte.  Reference rate = the
-                     # measured gather rate of the LDS pipe for uniformly random byte indices (tools/micro/lds_gather.hip:
-                     # 9.98 lanes per clock and CU at 16 waves per CU, 2.4 GHz nominal, 256 CUs; bank arithmetic: 64 /
-                     # (2 x 3.15)); long-list data runs at 1.07 of it, so it is a yardstick, not a ceiling.  It is NOT what
-                     # bounds the headline shape: with every gather compiled out the kernel takes 0.512 ms against 0.520
-                     # (profiles/r05_scan16_phases.txt section 4: an LDS / issue floor of 0.43 ms and a fabric-traffic
-                     # floor of 0.485 ms overlap to 0.52) -- reported beside the HBM fraction the contract asks for
-                     "lds_gather": {"achieved_per_clock_cu": code_bytes / (scan_ms * 1e-3) / 256 / 2.4e9 if scan_ms > 0 else 0.0,
-                                    "peak_per_clock_cu": 9.98,
-                                    "frac": code_bytes / (scan_ms * 1e-3) / 256 / 2.4e9 / 9.98 if scan_ms > 0 else 0.0}},
-        "stage_ms": {"coarse": prof_all["coarse_ms"] / 5, "tables": prof_all["tables_ms"] / 5,
-                     "scan": prof_all["scan_ms"] / 5, "note": "from 5 extra untimed steps with every stage instrumented"},
-    }
+    out["config"]["list_imbalance"] = round(list_stats(g, args.nlist)[1], 3)
+    out["config"]["ncode_per_query"] = ncode_per_launch / max(1, nq_rank)
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                        "kernel": "vlq::scan16_kernel", "kernel_ms": scan_ms,
+                        # `achieved` / `frac` are ALGORITHMIC code bytes over kernel time: an effective rate,
+                        # part of it served by L2 / Infinity Cache.  frac_measured = bytes the fabric counters saw over the
+                        # same time (null when no counter run matches this build and workload).
+                        "frac_measured": (traffic / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and scan_ms > 0) else None,
+                        "algorithmic_bytes": code_bytes,
+                        "lut_bytes_separate": lut_bytes,
+                        "lut_plus_code_GBps": (code_bytes + lut_bytes) / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0,
+                        # the kernel's other resource: one random 32-bit LDS gather per code byte.  Reference rate = the
+                        # measured gather rate of the LDS pipe for uniformly random byte indices (tools/micro/lds_gather.hip:
+                        # 9.98 lanes per clock and CU at 16 waves per CU, 2.4 GHz nominal, 256 CUs; bank arithmetic: 64 /
+                        # (2 x 3.15)); long-list data runs at 1.07 of it, so it is a yardstick, not a ceiling.  It is NOT what
+                        # bounds the headline shape: with every gather compiled out the kernel takes 0.512 ms against 0.520
+                        # (profiles/r05_scan16_phases.txt section 4: an LDS / issue floor of 0.43 ms and a fabric-traffic
+                        # floor of 0.485 ms overlap to 0.52) -- reported beside the HBM fraction the contract asks for
+                        "lds_gather": {"achieved_per_clock_cu": code_bytes / (scan_ms * 1e-3) / 256 / 2.4e9 if scan_ms > 0 else 0.0,
+                                       "peak_per_clock_cu": 9.98,
+                                       "frac": code_bytes / (scan_ms * 1e-3) / 256 / 2.4e9 / 9.98 if scan_ms > 0 else 0.0}}
+    out["stage_ms"] = {"coarse": prof_all["coarse_ms"] / 5, "tables": prof_all["tables_ms"] / 5,
+                        "scan": prof_all["scan_ms"] / 5, "note": "from 5 extra untimed steps with every stage instrumented"}
 
     out["config"]["all_gather_check"] = gather_ok       # asserted above: a wrong gather exits non-zero
     # the cold path (outside the timed region): single synchronous calls, host-timed -- each carries ~20 us of launch and
@@ -1188,10 +1254,7 @@ def main():
         import traceback
         out["post_run_error"] = "%s: %s" % (type(exc).__name__, str(exc)[:300])
         traceback.print_exc(file=sys.stderr)
-    print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

@@ -10,6 +10,9 @@ outputs), no reference source text.
 
     python tests/golden/make_golden.py            # all cases
     python tests/golden/make_golden.py c1_small   # one case
+
+`fullsize_c1` stores only the reference's answer (tests/golden/reference/fullsize_c1.npz) for the
+config-1-sized inputs that tests/util.py fullsize_inputs() generates, with a sha256 of those inputs.
 """
 import hashlib
 import os
@@ -211,7 +214,27 @@ def run_case(name):
                                                int(out["ncode"][0]), int(out["meta"][0])))
 
 
+def fullsize_c1():
+    """The reference's CPU IndexIVFPQ on the inputs of tests/test_gpu_fullsize.py (1 M codes, 10 000 queries): D, I and
+    its meta row, so that the GPU test compares with it on machines where the reference cannot run."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    from oracle import pyoracle, refbench
+    from util import FULLSIZE, FULLSIZE_REFERENCE, fullsize_inputs, inputs_sha
+    subprocess.check_call(["make", "-s", "-f", "oracle/ref.mk"], cwd=ROOT)
+    coarse, pq, codes, ids, off, xq = fullsize_inputs()
+    f = FULLSIZE
+    ox = pyoracle.OracleIndex(f["d"], f["nlist"], f["M"], 8, coarse, pq, codes=codes, ids=ids, list_offsets=off)
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "c1.faissindex")
+        refbench.write_ivfpq_index(path, ox.coarse_centroids, ox.pq_centroids, 8, ox.codes, ox.ids, ox.list_offsets)
+        D, I, _secs, meta = refbench.run_reference(path, xq, f["nprobe"], f["k"], reps=1, threads=8)
+    os.makedirs(os.path.dirname(FULLSIZE_REFERENCE), exist_ok=True)
+    np.savez_compressed(FULLSIZE_REFERENCE, D=D, I=I, meta=meta, inputs_sha256=inputs_sha(
+        ox.coarse_centroids, ox.pq_centroids, ox.codes, ox.ids, ox.list_offsets, xq))
+    print("%-18s %8.1f KB  mode=%d" % ("fullsize_c1", os.path.getsize(FULLSIZE_REFERENCE) / 1024.0, int(meta[0])))
+
+
 if __name__ == "__main__":
-    names = sys.argv[1:] or list(CASES)
+    names = sys.argv[1:] or list(CASES) + ["fullsize_c1"]
     for n in names:
-        run_case(n)
+        fullsize_c1() if n == "fullsize_c1" else run_case(n)

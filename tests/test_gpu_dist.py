@@ -7,20 +7,21 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_collective_path_with_hip_index():
+def test_bench_collective_path_with_hip_index(tmp_path):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
     e.update(BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
                         "--nb", "200000", "--nt", "50000", "--nlist", "1024", "--no-cpu-baseline", "--no-second-dataset",
-                        "--no-host-buffers", "--no-vlq"],
+                        "--no-host-buffers", "--no-vlq", "--full", "--dump-outputs", str(tmp_path)],
                        env=e, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -28,6 +29,9 @@ def test_bench_collective_path_with_hip_index():
     assert out["config"]["all_gather_check"] is True
     assert out["parity"]["distance_bits_equal"] is True and out["parity"]["label_mismatches"] == 0
     assert out["roofline"]["kernel_ms"] > 0 and "post_run_error" not in out
+    D, I = np.load(tmp_path / "distances.npy"), np.load(tmp_path / "labels.npy")
+    assert D.dtype == np.float32 and I.dtype == np.float64 and D.shape == I.shape == (10000, 10)
+    assert np.all(np.isfinite(D)) and I.min() >= 0 and I.max() < 200000
 
 
 def test_sharded_search_function_with_hip_index():

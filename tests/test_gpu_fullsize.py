@@ -7,26 +7,16 @@ import pytest
 
 import vector_line_quantization_amd as vlq
 from oracle import pyoracle
-from util import bits
+from util import FULLSIZE, FULLSIZE_REFERENCE, bits, fullsize_inputs, inputs_sha
 
 pytestmark = pytest.mark.gpu
 
-D_, NLIST, M, NB, NQ, NPROBE, K = 128, 4096, 16, 1000000, 10000, 32, 10
+D_, NLIST, M, NB, NQ, NPROBE, K = (FULLSIZE[n] for n in ("d", "nlist", "M", "nb", "nq", "nprobe", "k"))
 
 
 @pytest.fixture(scope="module")
 def world():
-    rng = np.random.default_rng(7)
-    coarse = rng.random((NLIST, D_), dtype=np.float32) * 255
-    pq = (rng.random((M, 256, D_ // M), dtype=np.float32) - 0.5) * 40
-    lens = rng.multinomial(NB, rng.dirichlet(np.full(NLIST, 0.7)))      # imbalanced lists
-    off = np.zeros(NLIST + 1, np.int64)
-    np.cumsum(lens, out=off[1:])
-    codes = rng.integers(0, 256, (NB, M), dtype=np.uint8)
-    codes[1000:1400] = codes[1000]                                       # exact ties inside a list
-    ids = rng.permutation(NB).astype(np.int64) * 3 + 1
-    # queries near centroids so that probes concentrate like real data
-    xq = (coarse[rng.integers(0, NLIST, NQ)] + rng.standard_normal((NQ, D_)) * 30).astype(np.float32)
+    coarse, pq, codes, ids, off, xq = fullsize_inputs()
     g = vlq.GpuIVFPQ(D_, NLIST, M, 8)
     g.set_coarse_centroids(coarse)
     g.set_pq_centroids(pq)
@@ -43,18 +33,17 @@ def test_sample_matches_oracle_bit_exact(world):
     assert np.array_equal(world["I"][sel], Io)
 
 
-def test_full_batch_vs_compiled_reference(world, tmp_path):
+def test_full_batch_vs_compiled_reference(world):
     """All 10 000 queries against the reference's own CPU IndexIVFPQ (oracle/_ref, built from the
-    reference's sources; skipped where that artefact is absent): same probe sets up to the BLAS
-    coarse stage's rounding, and wherever the label agrees the distance agrees to 1e-4 relative
-    (north-star tolerance) -- in practice bit for bit."""
-    from oracle import refbench
-    if not refbench.available():
-        pytest.skip("oracle/_ref not built")
+    reference's sources), whose answer for these inputs is stored in tests/golden/reference/: same
+    probe sets up to the BLAS coarse stage's rounding, and wherever the label agrees the distance
+    agrees to 1e-4 relative (north-star tolerance) -- in practice bit for bit."""
+    z = np.load(FULLSIZE_REFERENCE)
     ox = world["ox"]
-    path = str(tmp_path / "c1.faissindex")
-    refbench.write_ivfpq_index(path, ox.coarse_centroids, ox.pq_centroids, 8, ox.codes, ox.ids, ox.list_offsets)
-    Dr, Ir, secs, meta = refbench.run_reference(path, world["xq"], NPROBE, K, reps=1, threads=32)
+    assert np.array_equal(z["inputs_sha256"], inputs_sha(ox.coarse_centroids, ox.pq_centroids, ox.codes, ox.ids,
+                                                         ox.list_offsets, world["xq"])), \
+        "the stored reference answer belongs to other inputs: python tests/golden/make_golden.py fullsize_c1"
+    Dr, Ir, meta = z["D"], z["I"], z["meta"]
     D, I = world["D"], world["I"]
     assert meta[0] == 1
     from util import label_agreement

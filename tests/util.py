@@ -42,6 +42,36 @@ def sha(a):
     return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), dtype=np.uint8)
 
 
+FULLSIZE = dict(d=128, nlist=4096, M=16, nb=1000000, nq=10000, nprobe=32, k=10)
+FULLSIZE_REFERENCE = os.path.join(GOLDEN, "reference", "fullsize_c1.npz")
+
+
+def fullsize_inputs():
+    """BASELINE config-1 sizes with synthetic content (random centroids / codes, imbalanced lists, exact ties inside a
+    list, queries near centroids): coarse, pq, codes, ids, list offsets, queries.  Deterministic: the GPU test and the
+    stored reference answer (tests/golden/make_golden.py fullsize_c1) are built from the same arrays."""
+    d, nlist, M, nb, nq = (FULLSIZE[n] for n in ("d", "nlist", "M", "nb", "nq"))
+    rng = np.random.default_rng(7)
+    coarse = rng.random((nlist, d), dtype=np.float32) * 255
+    pq = (rng.random((M, 256, d // M), dtype=np.float32) - 0.5) * 40
+    lens = rng.multinomial(nb, rng.dirichlet(np.full(nlist, 0.7)))      # imbalanced lists
+    off = np.zeros(nlist + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    codes = rng.integers(0, 256, (nb, M), dtype=np.uint8)
+    codes[1000:1400] = codes[1000]                                       # exact ties inside a list
+    ids = rng.permutation(nb).astype(np.int64) * 3 + 1
+    # queries near centroids so that probes concentrate like real data
+    xq = (coarse[rng.integers(0, nlist, nq)] + rng.standard_normal((nq, d)) * 30).astype(np.float32)
+    return coarse, pq, codes, ids, off, xq
+
+
+def inputs_sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
+
+
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
