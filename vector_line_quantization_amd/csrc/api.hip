@@ -224,11 +224,6 @@ int coarse_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float*
         const int dp = (h->d + 15) / 16 * 16;
         TRY(h->ws_xh.reserve((size_t)n_pad * dp * 2));
         TRY(h->ws_xflags.reserve((size_t)n));
-        static const bool screen_stats = getenv("VLQ_SCREEN_STATS") != nullptr;       // kept columns per row, printed at destroy
-        if (screen_stats && !h->ws_kept.p) {
-            TRY(h->ws_kept.reserve(16));
-            HIP_TRY(hipMemsetAsync(h->ws_kept.p, 0, 16, h->stream));
-        }
         TRY(h->ws_cand.reserve(vlq::coarse_screen_keep_bytes(n, h->nlist)));
         if (h->nlist > 8192 || vlq::coarse_screen_matrix_free_ok(h->nlist, nprobe)) TRY(h->ws_tmin.reserve((size_t)n * (h->nlist / 16 + 32) * sizeof(float)));
         TRY(h->ws_qn_c.reserve((size_t)n * sizeof(float)));
@@ -238,7 +233,7 @@ int coarse_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float*
                                     h->ws_qn.as<float>(), h->cnorm.as<float>(), h->ws_qn_c.as<float>(), h->screen.norm_c.as<float>(),
                                     h->ws_dist.as<float>(), h->ws_tmin.p ? h->ws_tmin.as<float>() : nullptr, h->ws_cand.p, n, h->nlist,
                                     h->d, nprobe, h->screen.scale, h->screen.cmax, h->screen.cmax0, cdis_dev, keys_dev,
-                                    h->ws_kept.p ? h->ws_kept.as<unsigned long long>() : nullptr, h->ws_screen_cnt.as<unsigned int>(),
+                                    nullptr, h->ws_screen_cnt.as<unsigned int>(),
                                     h->stream, h->order_hist, &h->order_hist_ready);
         TRY(screen_counters_copy(h, n));
         HIP_TRY(hipGetLastError());
@@ -282,7 +277,7 @@ int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* cdis_de
     const int64_t n_pad = (n + 127) / 128 * 128;
     const size_t b_tab = (size_t)n_pad * kc * 4, b_sv = (size_t)n * T * 4, b_si = (size_t)n * T * 8;
     // (heap rows in global memory: only the thread-per-query replay of kernels.hip beyond its LDS sizes needs them)
-    const bool heap_rows = !(k <= 64 || vlq::imi_minsum_wide_ok(T, k, kc)) || getenv("VLQ_IMI_MINSUM_WIDE_FROM") || getenv("VLQ_IMI_MINSUM_LDS");
+    const bool heap_rows = !(k <= 64 || vlq::imi_minsum_wide_ok(T, k, kc)) || vlq::env().imi_minsum_lds;
     const size_t b_hv = heap_rows ? (size_t)n * 2 * k * 4 : 0, b_hi = heap_rows ? (size_t)n * 2 * k * 8 : 0, b_sub = (size_t)n * dc * 4;
     TRY(h->ws_imi.reserve(2 * b_tab + 2 * b_sv + 2 * b_si + b_hv + b_hi + 2 * b_sub + 256));
     char* p = h->ws_imi.as<char>();
@@ -303,8 +298,9 @@ int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* cdis_de
         h->coarse_screen = 0;                     // this index's data defeat the screen's bound: matrix path from here on
     // the radix select + one sort of imi_wide.hip against the running wave selection of kernels.hip (which stops at 1024):
     // coarse stage of 10 000 queries on 2 x 14 bits at 256 / 512 / 1024 cells 2.09 / 4.93 / 10.5 ms with the wave selection,
-    // 2.73 / 4.22 / 8.69 with the radix select
-    static const int radix_from = [] { const char* e = getenv("VLQ_IMI_RADIX_FROM"); return e ? atoi(e) : 400; }();
+    // 2.73 / 4.22 / 8.69 with the radix select.  A constant: from 400 on row_select_sorted_ok holds for every T (<= 4096, kc a
+    // power of two >= T), so the wave selection never gets more than its 1024 entries
+    constexpr int radix_from = 400;
     int64_t screened_rows = 0;       // rows that went through the two-pass screen (either half), counted once behind the join
     for (int m = 0; m < 2; m++) {
         const float* cent = h->imi_cent.as<float>() + (size_t)m * kc * dc;
@@ -338,8 +334,7 @@ int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* cdis_de
             // replay.
             const vlq_ivfpq_s::ScreenSet& sc = h->imi_screen[m];
             const int dp = (dc + 15) / 16 * 16;
-            static const bool one_stream = getenv("VLQ_IMI_ONE_STREAM") != nullptr;
-            const bool aux = m == 1 && !one_stream && !h->prof && h->imi_screen[0].ok && dc >= 16;
+            const bool aux = m == 1 && !h->prof && h->imi_screen[0].ok && dc >= 16;
             TRY(screen_counters(h));
             DevBuf& b_xh = aux ? h->imi_ws2.xh : h->ws_xh;
             DevBuf& b_xflags = aux ? h->imi_ws2.xflags : h->ws_xflags;
@@ -363,7 +358,7 @@ int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* cdis_de
                 }
                 st = h->imi_stream;
                 HIP_TRY(hipStreamWaitEvent(st, h->imi_fork, 0));        // (recorded before half 0 was issued: inputs and workspace ready)
-            } else if (m == 0 && !one_stream && !h->prof && h->imi_screen[1].ok) {
+            } else if (m == 0 && !h->prof && h->imi_screen[1].ok) {
                 if (!h->imi_stream) {
                     HIP_TRY(hipStreamCreateWithFlags(&h->imi_stream, hipStreamNonBlocking));
                     HIP_TRY(hipEventCreateWithFlags(&h->imi_fork, hipEventDisableTiming));
@@ -446,6 +441,7 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
              const float* cdis_dev, int nprobe, int k, float* D_dev, int64_t* I_dev,
              int store_pairs) {
     TRY(ensure_term2(h));
+    const vlq::Env& env = vlq::env();
     const size_t E = (size_t)h->M * h->ksub;
     const int table_mode = !h->by_residual ? 2 : (h->use_precomputed_table == 1 ? 1 : 0);
     if (h->imi_nbits > 0 && table_mode == 0)
@@ -455,7 +451,7 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
     // (and the 8 / 32 / 64-byte kernels of scanm.hip, any dsub, when they will serve the batch)
     const bool scanm_shape = table_mode == 1 && (h->M == 4 || h->M == 8 || h->M == 12 || (h->M >= 20 && h->M <= 32 && h->M % 4 == 0 && h->M != 16) ||
                                                  (h->M >= 40 && h->M <= 64 && h->M % 8 == 0)) && h->ksub == 256 &&
-                             h->ntotal >= (int64_t)h->nlist * 24 && !getenv("VLQ_GENERIC_SCAN") && !getenv("VLQ_SCANM_QTAB");
+                             h->ntotal >= (int64_t)h->nlist * 24 && !env.generic_scan;
     const bool fused_tables = (table_mode == 1 && h->M == 16 && h->ksub == 256 && h->dsub == 8) || scanm_shape;
     if (table_mode != 0 && !fused_tables)
         TRY(h->ws_qtab.reserve((size_t)std::min(n, page) * E * sizeof(float)));
@@ -501,7 +497,6 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         // 1.00 / 1.23 / 1.78 / 2.13 / 2.55 ms forced, more with the measured clock period; 64-byte codes 3.61 -> 3.47), and only when the batch's
         // neighbours share few lists
         // (walk_stat_kernel below).  VLQ_WALK_FIRST = n forces n probes in front for every batch, -1 the reference's order.
-        static const int wf_env = [] { const char* e = getenv("VLQ_WALK_FIRST"); return e ? atoi(e) : -2; }();
         const bool walk_base = table_mode == 1 && h->imi_nbits == 0 &&
                                ((h->M >= 12 && h->M <= 64 && h->M % 4 == 0) || (h->M == 8 && ni >= 3000)) &&
                                h->ksub == 256 && ni >= 1024 && !h->fp16_tables;
@@ -509,13 +504,10 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         // k 100: 1.51 -> 1.38 ms; at nprobe 32 nothing to gain: 0.81 = 0.81) on indexes of short lists
         const int walk_rule = !walk_base ? -1 : (k <= 64 && nprobe >= 16) ? 1
                             : (k <= 128 && nprobe >= 64 && h->ntotal < (int64_t)h->nlist * 1024) ? 4 : -1;
-        a.walk_first = wf_env >= -1 ? wf_env : walk_rule;
+        a.walk_first = env.walk_first >= -1 ? env.walk_first : walk_rule;
         {
-            static const int wc = [] { const char* e = getenv("VLQ_WALK_CLOCK"); return e ? atoi(e) : 0; }();       // > 0 fixed period, < 0 no clock
-            static const int wscale = [] { const char* e = getenv("VLQ_WALK_SCALE"); return e ? atoi(e) : 1000; }();
-            a.walk_clock = wc > 0 ? wc : 0;
-            a.walk_scale = wscale;
-            if (wc == 0 && a.walk_first >= 0) {
+            a.walk_clock = env.walk_clock > 0 ? env.walk_clock : 0;
+            if (env.walk_clock == 0 && a.walk_first >= 0) {
                 // the workgroups' own walk times, per XCD; a new (nprobe, k, batch class) starts measuring afresh
                 if (!h->walk_state.p) { TRY(h->walk_state.reserve(8 * 16 * sizeof(int))); h->walk_key = -1; }
                 const int64_t wkey = ((int64_t)nprobe << 32) ^ ((int64_t)k << 16) ^ (int64_t)(ni >= 4096 ? 2 : 1);
@@ -524,13 +516,12 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
             }
         }
         // the statistic is computed with the scan order (launch_query_order); behind the order's ni entries: its 32 counts
-        const bool walk_auto = wf_env < -1 && a.walk_first >= 0;
+        const bool walk_auto = env.walk_first < -1 && a.walk_first >= 0;
         // (the counts live in the handle: the statistic describes the workload, not one batch -- it is sampled on the first
         // four searches of a (nprobe, k, batch class) and on every 16th after that, 6.4 us + a launch gap otherwise saved per
-        // search; VLQ_WALK_STAT_EVERY=1: every search.  Speed only: the results do not depend on the walking order)
+        // search.  Speed only: the results do not depend on the walking order)
         if (walk_auto) TRY(h->walk_counts.reserve(32 * sizeof(int)));
-        static const int stat_every = [] { const char* e = getenv("VLQ_WALK_STAT_EVERY"); return e ? std::max(1, atoi(e)) : 16; }();
-        const bool walk_stat_now = walk_auto && (h->walk_stat_calls < 4 || h->walk_stat_calls % stat_every == 0);
+        const bool walk_stat_now = walk_auto && (h->walk_stat_calls < 4 || h->walk_stat_calls % 16 == 0);
         if (walk_auto) h->walk_stat_calls++;
         auto walk_part = [&]() -> int* { return walk_auto ? h->walk_counts.as<int>() : nullptr; };
         // a launch with no measured walk time seeds its clock period from a model (walk_stat_kernel): the workgroups that will
@@ -538,23 +529,32 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         vlq::WalkSeed wseed;
         wseed.list_off = h->list_off.as<int64_t>(); wseed.list_len = h->list_len.as<int64_t>(); wseed.nlist = h->nlist;
         wseed.slots = (int)std::min<int64_t>(ni, (k <= 128 && ni >= 3000 && h->ntotal < (int64_t)h->nlist * 1024) ? 2048 : (k <= 64 ? 1280 : 1024));
-        auto walk_decide = [&]() {        // after launch_query_order
-            if (!walk_auto || !a.qorder) return;
-            static const int share_max = [] { const char* e = getenv("VLQ_WALK_SHARE"); return e ? atoi(e) : 300; }();
-            const int samples = vlq::walk_stat_samples(ni, nprobe);
-            // from 128 probes on the list-id order won on both data sets (G1 2.26 -> 1.97 ms, headline 3.02 -> 2.48)
-            a.walk_limit = (int)((int64_t)samples * ((nprobe >= 128 && k <= 64) ? 1000 : share_max) / 1000);
-            a.walk_flag = walk_part();
-            if (getenv("VLQ_WALK_STAT_PRINT")) {
-                int v[32], tot = 0;
-                (void)hipStreamSynchronize(h->stream);
-                (void)hipMemcpy(v, a.walk_flag, sizeof(v), hipMemcpyDeviceToHost);
-                for (int x : v) tot += x;
-                int ws[8 * 16] = {0};
-                if (a.walk_state) (void)hipMemcpy(ws, a.walk_state, sizeof(ws), hipMemcpyDeviceToHost);
-                fprintf(stderr, "[vlq] walk order: neighbours share %d of %d sampled probes -> %s; walk ticks per XCD %d %d %d %d %d %d %d %d\n", tot, samples,
-                        tot <= a.walk_limit ? "list-id order" : "coarse-distance order", ws[0], ws[16], ws[32], ws[48], ws[64], ws[80], ws[96], ws[112]);
+        // run queries that share their nearest centroid next to each other (L2 reuse), take the walk statistic along and
+        // decide the walking order from it; booked with the table stage
+        auto order_queries = [&]() -> int {
+            if (ni < 1024 || h->nlist > (1 << 22)) return VLQ_OK;
+            StageTimer tq(h, 1);
+            TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
+            TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
+            vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream,
+                                    (h->have_rank && h->imi_nbits == 0) ? h->list_rank.as<int>() : nullptr, walk_part(), a.walk_state, wseed, walk_stat_now, h->order_hist_ready && ni == n);
+            a.qorder = h->ws_qorder.as<int>();
+            if (walk_auto) {
+                const int samples = vlq::walk_stat_samples(ni, nprobe);
+                // from 128 probes on the list-id order won on both data sets (G1 2.26 -> 1.97 ms, headline 3.02 -> 2.48)
+                a.walk_limit = (int)((int64_t)samples * ((nprobe >= 128 && k <= 64) ? 1000 : env.walk_share) / 1000);
+                a.walk_flag = walk_part();
             }
+            tq.stop();
+            return VLQ_OK;
+        };
+        // what the page's scan launch was (vlq_ivfpq_last_scan_info); walked: the scan took a's walking order
+        auto record_scan = [&](const char* shape, bool walked) {
+            snprintf(h->last_scan, sizeof(h->last_scan), "%s", shape);
+            h->last_walk_first = walked ? a.walk_first : -1;
+            h->last_walk_limit = walked ? a.walk_limit : 0;
+            h->last_walk_samples = walked && a.walk_flag ? vlq::walk_stat_samples(ni, nprobe) : 0;
+            h->last_walk_counts = walked && a.walk_flag != nullptr;   // (the 32 counts the order was decided from live in the handle)
         };
         const bool fast16 = table_mode == 1 && h->M == 16 && h->ksub == 256;
         if (h->fp16_tables && fast16 && h->imi_nbits == 0 && k <= 256) {
@@ -658,22 +658,10 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
                 tm.stop();
                 continue;
             }
-            if (ni >= 1024 && h->nlist <= (1 << 22)) {
-                StageTimer tq(h, 1);   // query ordering is booked with the table stage
-                // run queries that share their nearest centroid next to each other (L2 reuse)
-                TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
-                TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
-                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(),
-                                        h->ws_qorder.as<int>(), h->stream,
-                                        (h->have_rank && h->imi_nbits == 0) ? h->list_rank.as<int>() : nullptr, walk_part(), a.walk_state, wseed, walk_stat_now, h->order_hist_ready && ni == n);
-                a.qorder = h->ws_qorder.as<int>();
-                walk_decide();
-                tq.stop();
-            }
+            TRY(order_queries());
             StageTimer tm(h, 2);       // exactly the scan kernel
             if (h->ntotal < (int64_t)h->nlist * 24) {       // a few codes per list
                 vlq::launch_scan16_short(a, h->stream);
-                snprintf(h->last_scan, sizeof(h->last_scan), "scan16_short_kernel");
             }
             else {
                 // fewer workgroups than the chip holds (256 CUs x 4): split every query's probes over
@@ -711,8 +699,7 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
                     const int64_t rem = ni % slots;
                     int tp = rem > 0 ? (int)std::min<int64_t>(8, slots / rem) : 1;
                     tp = std::min(tp, nprobe / 4);
-                    static const bool tail_off = getenv("VLQ_NO_TAIL_SPLIT") != nullptr;
-                    if (ni > slots && ni < 2 * slots && tp >= 2 && k <= 128 && !tail_off) {
+                    if (ni > slots && ni < 2 * slots && tp >= 2 && k <= 128) {
                         vlq::ScanArgs at = a;
                         at.tail_r = (int)((rem + 7) / 8);
                         at.tail_p = tp;
@@ -732,43 +719,30 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
                 }
             }
             tm.stop();
-            if (h->ntotal >= (int64_t)h->nlist * 24) snprintf(h->last_scan, sizeof(h->last_scan), "%s", vlq::last_scan16_shape());
-            h->last_walk_first = a.walk_first; h->last_walk_limit = a.walk_limit;
-            h->last_walk_samples = a.walk_flag ? vlq::walk_stat_samples(ni, nprobe) : 0;
-            h->last_walk_counts = a.walk_flag != nullptr;       // (the 32 counts the order was decided from live in the handle)
-        } else if ((vlq::scanm_supports(a) || vlq::scanm0_supports(a)) && h->ntotal >= (int64_t)h->nlist * 24 && !getenv("VLQ_GENERIC_SCAN")) {
+            record_scan(h->ntotal >= (int64_t)h->nlist * 24 ? vlq::last_scan16_shape() : "scan16_short_kernel", true);
+        } else if ((vlq::scanm_supports(a) || vlq::scanm0_supports(a)) && h->ntotal >= (int64_t)h->nlist * 24 && !env.generic_scan) {
             // 8 / 32 / 64-byte codes: the engineered organisation (scanm.hip); queries ordered like the 16-byte path
-            if (ni >= 1024 && h->nlist <= (1 << 22)) {
-                StageTimer tq(h, 1);
-                TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
-                TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
-                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream,
-                                        (h->have_rank && h->imi_nbits == 0) ? h->list_rank.as<int>() : nullptr, walk_part(), a.walk_state, wseed, walk_stat_now, h->order_hist_ready && ni == n);
-                a.qorder = h->ws_qorder.as<int>();
-                walk_decide();
-                tq.stop();
-            }
+            TRY(order_queries());
             StageTimer tm(h, 2);
             vlq::launch_scanm(a, h->stream);
             tm.stop();
-            snprintf(h->last_scan, sizeof(h->last_scan), "scanm_kernel<%d>", h->M);
-            h->last_walk_first = a.walk_first; h->last_walk_limit = a.walk_limit;
-            h->last_walk_samples = a.walk_flag ? vlq::walk_stat_samples(ni, nprobe) : 0;
-            h->last_walk_counts = a.walk_flag != nullptr;
-        } else if (h->M != 16 && h->ntotal < (int64_t)h->nlist * 24 && vlq::scanm_short_supports(a) && !getenv("VLQ_GENERIC_SCAN")) {
+            char shape[32];
+            snprintf(shape, sizeof(shape), "scanm_kernel<%d>", h->M);
+            record_scan(shape, true);
+        } else if (h->M != 16 && h->ntotal < (int64_t)h->nlist * 24 && vlq::scanm_short_supports(a) && !env.generic_scan) {
             // a few codes per list, any engineered code size but 16 bytes (the multi-index drivers ship 8): no table per probe,
             // each lane fetches the entries its code addresses (scanm_short.hip)
             StageTimer tm(h, 2);
             vlq::launch_scanm_short(a, h->stream);
             tm.stop();
-            snprintf(h->last_scan, sizeof(h->last_scan), "scanm_short_kernel<%d>", h->M);
-            h->last_walk_first = -1; h->last_walk_limit = 0; h->last_walk_samples = 0; h->last_walk_counts = false;
+            char shape[32];
+            snprintf(shape, sizeof(shape), "scanm_short_kernel<%d>", h->M);
+            record_scan(shape, false);
         } else {
             StageTimer tm(h, 2);
             vlq::launch_scan(a, h->stream);
             tm.stop();
-            snprintf(h->last_scan, sizeof(h->last_scan), "scan_kernel");
-            h->last_walk_first = -1; h->last_walk_limit = 0; h->last_walk_samples = 0; h->last_walk_counts = false;
+            record_scan("scan_kernel", false);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -859,7 +833,6 @@ int vlq_ivfpq_create(vlq_ivfpq_t* out, int device, int d, int nlist, int M, int 
         const int m = atoi(e);
         if (m >= 0 && m <= 4) h->scan_schedule = m;
     }
-    if (const char* e = getenv("VLQ_COARSE_SCREEN")) h->coarse_screen = atoi(e);   // 0: f32 MFMA matrix path everywhere (A/B)
     if (const char* e = getenv("VLQ_COARSE_FILTER")) h->coarse_filter = atoi(e);   // 1: filtered coarse stage (A/B; slower)
     h->h_lists_stale = true;    // host copies of the list starts / lengths are filled on first use
     int rc = h->stats.reserve(512);    // [0] ncode, [1] flag word; [2..7] phase clocks of instrumented builds (-DVLQ_PHASE_TIMING), [8..47] (-DVLQ_SCAN16_PHASES)
@@ -896,12 +869,6 @@ void vlq_ivfpq_destroy(vlq_ivfpq_t h) {
                       &h->ws_qn_c, &h->ws_xh, &h->ws_xflags, &h->ws_screen_cnt};
     for (auto b : bufs) b->release();
     if (h->screen_cnt_host) (void)hipHostFree(h->screen_cnt_host);
-    if (h->ws_kept.p) {
-        unsigned long long kept = 0;
-        (void)hipMemcpy(&kept, h->ws_kept.p, 8, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[vlq] coarse screen: %llu columns kept in total\n", kept);
-        h->ws_kept.release();
-    }
     for (DevBuf* b : {&h->imi_ws2.xh, &h->imi_ws2.xflags, &h->imi_ws2.qn, &h->imi_ws2.qn_c, &h->imi_ws2.cand, &h->imi_ws2.tmin}) b->release();
     if (h->imi_fork) (void)hipEventDestroy(h->imi_fork);
     if (h->imi_join) (void)hipEventDestroy(h->imi_join);
@@ -1353,7 +1320,7 @@ int vlq_ivfpq_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe, int k
     // (kernels.h OrderHist; the single-workgroup ordering of small batches does not use it)
     h->order_hist = vlq::OrderHist();
     h->order_hist_ready = false;
-    if (h->imi_nbits == 0 && n > 2048 && n <= 32768 && n <= query_page(h) && h->nlist <= (1 << 22) && !getenv("VLQ_ORDER_HIST_OFF")) {
+    if (h->imi_nbits == 0 && n > 2048 && n <= 32768 && n <= query_page(h) && h->nlist <= (1 << 22)) {
         const size_t stride = vlq::query_order_bins_padded(h->nlist);
         TRY(h->ws_hist.reserve(2 * stride * sizeof(int)));
         HIP_TRY(hipMemsetAsync(h->ws_hist.p, 0, 2 * stride * sizeof(int), h->stream));
@@ -1410,7 +1377,7 @@ int vlq_ivfpq_stats(vlq_ivfpq_t h, uint64_t* nq, uint64_t* ncode, int reset) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (nq) *nq = h->stat_nq;
     if (ncode) *ncode = st[0];
-    if (st[8 + 14] && getenv("VLQ_SCAN16_PHASES")) {    // only a scan16 built with -DVLQ_SCAN16_PHASES writes these (scan16.hip)
+    if (st[8 + 14] && vlq::env().scan16_phases) {    // only a scan16 built with -DVLQ_SCAN16_PHASES writes these (scan16.hip)
         static const char* names[14] = {"set-up: second barrier, first prefetch", "barrier before the table build", "wait for the prefetched row (vmcnt)",
                                         "table build + next prefetch issued", "barrier after the build", "admission bound refresh",
                                         "gather trips + selection", "merge + rows out", "set-up: placement", "set-up: probe keys, list offsets",
@@ -1432,7 +1399,7 @@ int vlq_ivfpq_stats(vlq_ivfpq_t h, uint64_t* nq, uint64_t* ncode, int reset) {
             }
         }
     }
-    if (st[5] && getenv("VLQ_PHASE_TIMING"))     // only kernels built with -DVLQ_PHASE_TIMING write these
+    if (st[5] && vlq::env().phase_timing)     // only kernels built with -DVLQ_PHASE_TIMING write these
         fprintf(stderr, "[phase timing] per workgroup: prologue %.2f us, loop %.2f us, tail %.2f us (%llu workgroups)\n",
                 st[2] * 0.01 / st[5], st[3] * 0.01 / st[5], st[4] * 0.01 / st[5], st[5]);
     const int bad = (int)(st[1] & 0xffffffffu);

@@ -170,9 +170,6 @@ __global__ __launch_bounds__(256) void coarse_f16_dist_kernel(const _Float16* __
 // The approximate distance is a = qn_c + v', v' = fma(-2 / s^2, ip~, cn_c); both passes compute v' by the same operation, the
 // bound kernel adds qn_c (monotone: the nprobe-th smallest class minimum of v' gives the nprobe-th smallest of a) and hands
 // pass 1 the bound minus qn_c, rounded up.
-#ifndef VLQ_STREAM_ABL
-#define VLQ_STREAM_ABL 0          // timing experiments (wrong results): 1 no epilogue, 2 no MFMA, 4 no stage copies, 8 no LDS fragment reads
-#endif
 template <int KS, int PASS>
 __global__ __launch_bounds__(256, 2) void coarse_f16_stream_kernel(const _Float16* __restrict__ Qh, const _Float16* __restrict__ Ch,
                                                                    const float* __restrict__ cn, int64_t nq, int nlist, int nb_range,
@@ -856,9 +853,6 @@ __global__ __launch_bounds__(256) void coarse_screen_exact_kernel(const uint32_t
     WaveSelect<KPL> sel;
     sel.init(nprobe, queue[wave], lane);
     __builtin_amdgcn_wave_barrier();
-#ifdef VLQ_EXACT_PROLOGUE_ONLY
-    if (total >= 0) { if (lane == 0) cdis[q * nprobe] = (float)total; return; }
-#endif
     if (!exact_row) {
         float* st = stage[wave];
         for (int c0 = 0; c0 < total; c0 += 64) {
@@ -991,16 +985,12 @@ size_t coarse_screen_keep_bytes(int64_t nq, int nlist) {
 }
 // the matrix-free form: a pool of 32 class minima per (super-)range of 512 x nsub columns, at most 1024 per row, at least
 // 2 nprobe of them; round 5: up to 16 384 lists and 64 probes; round 6: up to 2^20 lists (nsub ranges per workgroup) and 128 probes
-// (VLQ_COARSE_MATRIX_FREE_WIDE=0: round 5's limits, the half-matrix form beyond them)
 static int matrix_free_nsub(int nlist) {
     const int nranges = ((nlist >> 5) + 15) / 16;
     return (nranges + 31) / 32;
 }
 bool coarse_screen_matrix_free_ok(int nlist, int nprobe) {
-    static const bool off = getenv("VLQ_COARSE_MATRIX") != nullptr;      // A/B: the half matrix of rounds 3-4
-    static const bool wide = !(getenv("VLQ_COARSE_MATRIX_FREE_WIDE") && atoi(getenv("VLQ_COARSE_MATRIX_FREE_WIDE")) == 0);
-    if (off || nlist < 1024 || (nlist & 63)) return false;
-    if (!wide && (nlist > 16384 || nprobe > 64)) return false;
+    if (nlist < 1024 || (nlist & 63)) return false;
     const int nranges = ((nlist >> 5) + 15) / 16;
     const int nsuper = (nranges + matrix_free_nsub(nlist) - 1) / matrix_free_nsub(nlist);
     return nlist <= (1 << 20) && nprobe <= 128 && nprobe * 2 <= 32 * nsuper;

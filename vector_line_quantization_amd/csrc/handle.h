@@ -117,7 +117,7 @@ struct vlq_ivfpq_s {
     // centred squared norms, the power-of-two scale, max |c - mu|, max |c|
     struct ScreenSet { DevBuf half, mu, norm_c; float scale = 1.f, cmax = 0.f, cmax0 = 0.f; bool ok = false; };
     ScreenSet screen, imi_screen[2];
-    DevBuf ws_qn_c, ws_xh, ws_xflags, ws_kept, ws_screen_cnt;
+    DevBuf ws_qn_c, ws_xh, ws_xflags, ws_screen_cnt;
     // second half of a multi-index coarse stage, screened beside the first on an auxiliary stream (imi_page): its own copies
     // of the per-half workspaces, the stream, fork / join events
     struct HalfWs { DevBuf xh, xflags, qn, qn_c, cand, tmin; } imi_ws2;

@@ -3,8 +3,40 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace vlq {
+
+// The library's run-time switches, read once per process.  None changes a result: each pins a path that a test or a
+// measuring tool compares against the default.  VLQ_SCAN_SCHEDULE and VLQ_COARSE_FILTER are per-index
+// settings, read by vlq_ivfpq_create.
+struct Env {
+    int walk_first = -2;       // VLQ_WALK_FIRST: probes in front of the list-id walk, -1 the reference's order, -2 automatic (tests/test_gpu_walk_order.py, tests/test_gpu_ties.py)
+    int walk_share = 300;      // VLQ_WALK_SHARE: shared probes per 1000 samples up to which the batch walks in list-id order (tests/test_gpu_walk_order.py)
+    int walk_clock = 0;        // VLQ_WALK_CLOCK: > 0 fixed walk-clock period in 10 ns ticks, < 0 no clock (tests/test_gpu_walk_order.py, tests/test_gpu_ties.py)
+    int scan16_variant = -1;   // VLQ_SCAN16_VARIANT: 4 two waves, 1 four waves per 16-byte scan workgroup; other values ignored (tests/test_gpu_walk_order.py)
+    bool generic_scan = false;   // VLQ_GENERIC_SCAN: the generic scan_kernel for every code size (tests/test_gpu_code_sizes.py)
+    bool imi_minsum_lds = false; // VLQ_IMI_MINSUM_LDS: the thread-per-query MinSumK walk (tests/test_gpu_imi_minsum.py)
+    bool phase_timing = false;   // VLQ_PHASE_TIMING: print the phase clocks of a -DVLQ_PHASE_TIMING build of scan16o.hip (tools/owned_probe.py)
+    bool scan16_phases = false;  // VLQ_SCAN16_PHASES: print the phase clocks of a -DVLQ_SCAN16_PHASES build (tools/scan16_phases.py)
+    bool l16c_timing = false;    // VLQ_L16C_TIMING: print the phase clocks of a -DVLQ_L16C_TIMING build of line16c.hip (tools/build_variant.sh)
+};
+inline const Env& env() {
+    static const Env e = [] {
+        Env v;
+        if (const char* s = getenv("VLQ_WALK_FIRST")) v.walk_first = atoi(s);
+        if (const char* s = getenv("VLQ_WALK_SHARE")) v.walk_share = atoi(s);
+        if (const char* s = getenv("VLQ_WALK_CLOCK")) v.walk_clock = atoi(s);
+        if (const char* s = getenv("VLQ_SCAN16_VARIANT")) { const int x = atoi(s); if (x == 1 || x == 4) v.scan16_variant = x; }
+        v.generic_scan = getenv("VLQ_GENERIC_SCAN") != nullptr;
+        v.imi_minsum_lds = getenv("VLQ_IMI_MINSUM_LDS") != nullptr;
+        v.phase_timing = getenv("VLQ_PHASE_TIMING") != nullptr;
+        v.scan16_phases = getenv("VLQ_SCAN16_PHASES") != nullptr;
+        v.l16c_timing = getenv("VLQ_L16C_TIMING") != nullptr;
+        return v;
+    }();
+    return e;
+}
 
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to `bytes` on
 // the CURRENT device.  The attribute is per device and the library may serve several devices
@@ -145,7 +177,7 @@ struct ScanArgs {
     int* walk_state = nullptr;       // per XCD (16 ints apart): running mean of a workgroup's walk time, kept across launches
     int walk_scale = 1000;           // period = measured walk time x this / 1000
     int walk_limit = 0;              // ... list-id order only while their sum is <= this
-    int short_keep_order = 0;    // scan16_short: walk a query's multi-index cells in coarse order (A/B: VLQ_SHORT_KEEP_ORDER) instead of by halves
+    int short_keep_order = 0;    // scan16_short: walk a query's multi-index cells in coarse order instead of by halves (retired A/B: always 0)
     int walk_first = -1;         // walk_order.cuh: < 0 = probes in coarse-distance order, else this many nearest first, the rest by list id
     int grid_per_xcd = 0;        // set by the launcher: workgroups per XCD (xcd_chunk unless the tail is split)
     // list-owned schedule (scan16 only, DESIGN.md "list-owned schedule"): the lists are cut into 8

@@ -644,7 +644,6 @@ static void launch_coarse_areg_t(const float* q, const float* c, const float* qn
         if (per_cu < 2 && blocks > 256 / 2) cost *= 1.1;        // lone workgroups: nothing hides their barriers
         if (cost < best_cost) { best_cost = cost; best_t = tpb; }
     }
-    if (const char* e = getenv("VLQ_COARSE_TPB")) { const int v = atoi(e); if (v >= 1 && v <= 64) best_t = v; }   // A/B only
     dim3 grid((unsigned)rb, (unsigned)((ntiles + best_t - 1) / best_t));
     hipLaunchKernelGGL((coarse_dist_areg_kernel<NU, VEC, TMIN>), grid, dim3(256), smem, s, q, c, qn, cn, out,
                        nq, nlist, d, best_t, tmin, flt);
@@ -654,10 +653,10 @@ template <int NU>
 static void launch_coarse_areg(const float* q, const float* c, const float* qn, const float* cn,
                                float* out, int64_t nq, int nlist, int d, float* tmin, hipStream_t s, int64_t out_rows) {
     if (tmin && !out) launch_coarse_areg_t<NU, true, 3>(q, c, qn, cn, out, nq, nlist, d, tmin, s);   // coarse_argmin_ok
-    else if (tmin && out_rows >= (nq + 127) / 128 * 128 && !getenv("VLQ_COARSE_PLAIN"))
+    else if (tmin && out_rows >= (nq + 127) / 128 * 128)
         launch_coarse_areg_t<NU, true, 8>(q, c, qn, cn, out, nq, nlist, d, tmin, s);                   // coarse_tile_minima_ok, pipelined
     else if (tmin) launch_coarse_areg_t<NU, true, 1>(q, c, qn, cn, out, nq, nlist, d, tmin, s);       // coarse_tile_minima_ok
-    else if (d % 4 == 0 && d >= 4 && nlist % 64 == 0 && out_rows >= (nq + 127) / 128 * 128 && !getenv("VLQ_COARSE_PLAIN")) {
+    else if (d % 4 == 0 && d >= 4 && nlist % 64 == 0 && out_rows >= (nq + 127) / 128 * 128) {
         // plain matrix, whole tiles, and the matrix has room for whole 128-row blocks (rows past nq are written and
         // never read): the pipelined loop, whose epilogue has no row guard
         launch_coarse_areg_t<NU, true, 7>(q, c, qn, cn, out, nq, nlist, d, nullptr, s);
@@ -1740,8 +1739,7 @@ void launch_imi_minsum(const float* sv0, const int64_t* si0, const float* sv1, c
                        int64_t nq, int k, int kc, int imi_nbits, float* heap_val, int64_t* heap_id,
                        float* sums, int64_t* keys, hipStream_t s) {
     if (nq <= 0) return;
-    static const bool no_wave = getenv("VLQ_IMI_MINSUM_LDS") != nullptr;       // (A/B: the thread-per-query walk)
-    if (k > 1 && k <= 64 && T <= 64 && kc <= 32768 && !no_wave) {
+    if (k > 1 && k <= 64 && T <= 64 && kc <= 32768 && !env().imi_minsum_lds) {
         constexpr int NW = 4;
         hipLaunchKernelGGL(imi_minsum_wave_kernel<NW>, dim3((unsigned)((nq + NW - 1) / NW)), dim3(64 * NW), 0, s,
                            sv0, si0, sv1, si1, T, nq, k, kc, imi_nbits, sums, keys);
@@ -1749,9 +1747,8 @@ void launch_imi_minsum(const float* sv0, const int64_t* si0, const float* sv1, c
     }
     // beyond 64 cells: one wave per query with its heap in LDS, the lanes sharing a sift's comparisons (imi_wide.hip; 10 000
     // queries, 2 x 14 bits, k = 128: 1.09 ms against the thread-per-query kernel's 1.55, whose 32 heaps per workgroup stop
-    // fitting LDS at 128 and then live in global memory -- VLQ_IMI_MINSUM_WIDE_FROM=129 for the A/B)
-    static const int wide_from = getenv("VLQ_IMI_MINSUM_WIDE_FROM") ? atoi(getenv("VLQ_IMI_MINSUM_WIDE_FROM")) : 65;
-    if (k >= wide_from && imi_minsum_wide_ok(T, k, kc)) {
+    // fitting LDS at 128 and then live in global memory)
+    if (k > 64 && imi_minsum_wide_ok(T, k, kc)) {
         launch_imi_minsum_wide(sv0, si0, sv1, si1, T, nq, k, kc, imi_nbits, sums, keys, s);
         return;
     }

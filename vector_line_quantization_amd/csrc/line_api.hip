@@ -482,14 +482,13 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
         // it and the line select that gathers from it were measured and lose: 2000 queries in pages of 500 / 1000 queries 3.22 /
         // 3.06 ms against 2.98 for one page -- the smaller launches cost more than the cache returns.)
         const int64_t sub = ni;
-        static const bool ls_old = getenv("VLQ_LINE_SELECT_WAVE") != nullptr;     // A/B: the one-wave-per-query kernel
         for (int64_t j0 = 0; j0 < ni; j0 += sub) {
             const int64_t nj = std::min(sub, ni - j0);
             // 1. all centroid "distances" without |q|^2 + the nprobe nearest (Distance.cu:233-383)
             TRY(coarse_page(b, nj, xi + j0 * b->d, nprobe, h->ws_cdis.as<float>(), h->ws_keys.as<int64_t>(), true, false, true));
             // 2. the w1 best lines among nprobe x nedge (BroadcastSum.cu:477-560)
             vlq::LineMeta* metaj = with_meta ? h->ws_sel_meta.as<vlq::LineMeta>() + j0 * w1 : nullptr;
-            if (!ls_old && vlq::line_select2_supports(nprobe, h->nedge, w1))
+            if (vlq::line_select2_supports(nprobe, h->nedge, w1))
                 vlq::launch_line_select2(b->ws_dist.as<float>(), nj, b->nlist, h->ws_keys.as<int64_t>(), nprobe,
                                          h->edge_info.as<int32_t>(), h->edge_dist.as<float>(), h->nedge, w1,
                                          sel_line + j0 * w1, h->ws_sel_b2.as<float>() + j0 * w1, h->ws_sel_g.as<float>() + j0 * w1,
@@ -592,7 +591,7 @@ int vlq_line_stats(vlq_line_t h, uint64_t* ncode, int reset) {
     HIP_TRY(hipMemcpyAsync(st, h->stats.p, 64, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (ncode) *ncode = st[0];
-    if (getenv("VLQ_L16C_TIMING") && st[5])
+    if (vlq::env().l16c_timing && st[5])
         fprintf(stderr, "[l16c timing] per workgroup: prologue %.2f us, loop %.2f us, tail %.2f us (%llu workgroups)\n",
                 st[2] * 0.01 / st[5], st[3] * 0.01 / st[5], st[4] * 0.01 / st[5], st[5]);
     if (reset) HIP_TRY(hipMemsetAsync(h->stats.p, 0, 64, b->stream));

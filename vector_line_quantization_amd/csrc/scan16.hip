@@ -30,13 +30,6 @@ namespace vlq {
 // s_memtime = shader cycles; sums per phase of a sample of workgroups go to stats[8 + 20 * wave ..] (vlq_ivfpq_stats prints
 // them); no result is computed from a stamp.  The build also waits for the prefetched row explicitly before the table build,
 // so that waiting for memory and storing the table are two phases.
-// Ablation builds (tools/build_variant.sh ablN "-DVLQ_SCAN16_ABL=N" scan16): kernel TIME with one part of the probe loop removed --
-// results are wrong under every one of them.  Bits: 1 no selection, 2 no gathers, 4 no table stores, 8 no row loads, 16 no code reloads
-#ifndef VLQ_SCAN16_ABL
-#define VLQ_SCAN16_ABL 0
-#endif
-static constexpr bool kAblSelect = (VLQ_SCAN16_ABL & 1) != 0, kAblGather = (VLQ_SCAN16_ABL & 2) != 0, kAblStore = (VLQ_SCAN16_ABL & 4) != 0,
-                      kAblRows = (VLQ_SCAN16_ABL & 8) != 0, kAblCodes = (VLQ_SCAN16_ABL & 16) != 0;
 #ifdef VLQ_SCAN16_PHASES
 #define VLQ_PH_DECL                                              \
     uint64_t ph_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
@@ -291,10 +284,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
         // loads otherwise queue behind the gathers of the CU's other workgroups (scan 0.665 ->
         // 0.655 ms at the headline shape; levels 1..3 measure the same)
         __builtin_amdgcn_s_setprio(2);
-        if (kAblStore) {
-#pragma unroll
-            for (int i2 = 0; i2 < NI; i2++) asm volatile("" :: "v"(t2r[i2].x), "v"(t2r[i2].y), "v"(t2r[i2].z), "v"(t2r[i2].w));
-        } else build_lut16<NI>(L, t, t2r, m2t3);
+        build_lut16<NI>(L, t, t2r, m2t3);
         uint4 cc = cr[0], cd = cr[1];
         // a list longer than NPRE chunks: its next two chunks requested now (the row registers are free once the table is
         // stored), in flight across the barrier (four until the keyed admission arrived: at 128 VGPRs the two-wave shape
@@ -405,22 +395,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
                     const uint32_t jc = w64 + C * NT;
                     uint32_t g = jc < len ? 1u : 0u;      // (wave-uniform)
                     float lo[8], hi[8];
-                    if (g && !kAblGather) {
+                    if (g) {
                         VLQ_PH_TRIP();
                         VLQ_PH_G0();
                         const uint4 cur = cr[C];
                         if (B == 0) { { float (&v)[8] = lo; VLQ_G8LO_NW(0, cur.x, cur.y); } { float (&v)[8] = hi; VLQ_G8HI_NW(0, cur.z, cur.w); } }
                         else { { float (&v)[8] = lo; VLQ_G8LO_NW(16384, cur.x, cur.y); } { float (&v)[8] = hi; VLQ_G8HI_NW(16384, cur.z, cur.w); } }
                     }
-                    if (!kAblCodes) load_chunk(cc_);
-                    if (C == 0 && !kAblRows) load_rows();
+                    load_chunk(cc_);
+                    if (C == 0) load_rows();
                     g = __builtin_amdgcn_readfirstlane(g);
                     asm volatile("" : "+s"(g));        // (keeps the two halves of the trip from being threaded into two copies of the loads)
-                    if (g && kAblGather) {
-                        const uint4 cur = cr[C];
-                        if (kAblSelect) asm volatile("" :: "v"(cur.x)); else sel.offer_keyed(dis0 + __uint_as_float(cur.x & 0x3fffffffu), pos0 + jc + lane, jc + lane < len);
-                    }
-                    if (g && !kAblGather) {
+                    if (g) {
                         float dis = dis0;
                         VLQ_WAIT8(8, lo);
 #pragma unroll
@@ -430,8 +416,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
 #pragma unroll
                         for (int m = 0; m < 8; m++) dis = __fadd_rn(dis, hi[m]);
                         VLQ_PH_G1();
-                        if (kAblSelect) asm volatile("" :: "v"(dis));
-                        else sel.offer_keyed(dis, pos0 + jc + lane, jc + lane < len);
+                        sel.offer_keyed(dis, pos0 + jc + lane, jc + lane < len);
                     }
                 };
                 trip(std::integral_constant<int, 0>{});
@@ -781,8 +766,7 @@ void launch_scan16_short(const ScanArgs& a_in, hipStream_t s) {
     if (a_in.nq <= 0) return;
     ScanArgs a = a_in;
     a.xcd_chunk = (int)((a.nq + 7) / 8);
-    static const bool keep_order = getenv("VLQ_SHORT_KEEP_ORDER") != nullptr;
-    a.short_keep_order = keep_order ? 1 : 0;
+    a.short_keep_order = 0;          // (multi-index cells by halves; the coarse-order walk was a retired A/B)
     size_t region = (size_t)4096 * 4;                        // the merge area aliases the table
     const size_t merge = (size_t)4 * a.k * 8;
     if (region < merge) region = merge;
@@ -849,8 +833,7 @@ void launch_scan16(const ScanArgs& a_in, hipStream_t s) {
     // queries: G1 data 0.649 -> 0.606 ms (0.97 of the LDS gather rate), headline data 0.730 = 0.730 (row traffic bound); 2500
     // queries 0.230 -> 0.215 / 0.192 -> 0.179 ms: 1280 slots hold a sharded batch's slice in fewer rounds.  Long lists keep two
     // buffers and the pair loop (two chunks per trip, the adds of one under the gathers of the other).
-    // VLQ_SCAN16_VARIANT (A/B): 0 = two buffers + pair loop always, 2 = two buffers, plain loop, 3 = one buffer, pair loop.
-    static const int variant = [] { const char* e = getenv("VLQ_SCAN16_VARIANT"); return e ? atoi(e) : -1; }();
+    const int variant = env().scan16_variant;
     const bool plain = !a.part_keys && a.imi_nbits == 0;
     // ... and from 3000 queries on TWO waves per workgroup (a thread owns 32 table entries: 127 VGPRs, 8 workgroups per CU = 2048
     // slots): a list of 330 codes is 3 trips of 128 lanes instead of 2 trips of 256 -- 25 % fewer lane slots, and a two-wave
@@ -864,17 +847,8 @@ void launch_scan16(const ScanArgs& a_in, hipStream_t s) {
     } else if (a.k <= 64 && plain && (variant == 1 || (variant < 0 && !a.long_lists))) {
         const size_t l1 = std::max((size_t)4096 * 4, merge);
         launch_scan16_t<1, 4, 1, false>(a, (int)l1, l1 + tail, s);
-    } else if (a.k <= 64 && variant == 6 && plain && !a.tail_r && a.nsplit == 1) {
-        // two waves AND two table buffers (one barrier per probe; 33 KB of LDS = 4 workgroups per CU)
-        const size_t l2 = std::max((size_t)2 * 4096 * 4, (size_t)2 * a.k * 8);
-        const size_t tail2 = (size_t)2 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64 + wrec;
-        launch_scan16_t<1, 2, 2, false>(a, (int)l2, l2 + tail2, s);
-    } else if (a.k <= 64 && variant == 2 && plain) launch_scan16_t<1, 4, 2, false>(a, (int)lutb, smem, s);
-    else if (a.k <= 64 && variant == 3 && plain) {
-        const size_t l1 = std::max((size_t)4096 * 4, merge);
-        launch_scan16_t<1, 4, 1, true>(a, (int)l1, l1 + tail, s);
     } else if (a.k <= 64) launch_scan16_t<1, 4, 2, true>(a, (int)lutb, smem, s);
-    else if (a.k <= 128 && plain && !a.tail_r && a.nsplit == 1 && (variant == 5 || (variant < 0 && !a.long_lists && a.nq >= 3000))) {
+    else if (a.k <= 128 && plain && !a.tail_r && a.nsplit == 1 && variant < 0 && !a.long_lists && a.nq >= 3000) {
         // two waves per workgroup as for k <= 64 (128 VGPRs forced): k = 100, 10 000 queries: headline data 0.815 -> 0.77 ms,
         // nprobe 64 1.34 -> 1.13, G1 0.75 -> 0.68
         const size_t l1 = std::max((size_t)4096 * 4, (size_t)2 * a.k * 8);

@@ -301,11 +301,7 @@ __global__ __launch_bounds__(64 * (NWX ? NWX : ScanMShape<M>::NW)) __attribute__
     // waited for vmcnt(0) in every trip: for the NEXT probe's row and codes, requested just before the barrier).
     // 8-byte codes: TWO probes ahead (DEPTH 2, register sets alternating with the table buffers): three trips of 8 gathers
     // are over long before a row requested one probe earlier has crossed the fabric.
-    #ifdef VLQ_SCANM8_OLD
-    constexpr bool AHEAD = DSUB == 0 && KPL <= 2 && M == 32;
-#else
     constexpr bool AHEAD = DSUB == 0 && KPL <= 2;
-#endif
     constexpr int DEPTH = (AHEAD && NBUF == 2) ? 2 : 1;
     constexpr int NPRE = M == 8 ? 3 : 2;           // chunks of a list requested ahead (32-byte codes: registers)
     constexpr int NEX = M == 8 ? 4 : 1;            // chunks of a longer list in flight at a time
@@ -591,8 +587,7 @@ static void launch_scanm_k(const ScanArgs& a, hipStream_t s) {
     // 8-byte codes, k <= 64, 3000 queries and more: two waves per workgroup.  The kernel is bound by the instructions it issues
     // (profiles/r05_code_sizes.txt: 4100 VALU + 2400 SALU per wave at four waves, 3/4 of them per-probe work every wave
     // repeats -- metadata, addresses, table build, threshold -- for 1.3 trips of 8 gathers); two waves halve that share
-    static const int nw8_env = [] { const char* e = getenv("VLQ_SCANM8_WAVES"); return e ? atoi(e) : 0; }();
-    if (M == 8 && a.k <= 64 && (nw8_env ? nw8_env == 2 : a.nq * a.nsplit >= 3000)) {
+    if (M == 8 && a.k <= 64 && a.nq * a.nsplit >= 3000) {
         if (a.imi_nbits > 0) launch_scanm_i<M, 1, NBUF, true, 0, M == 8 ? 2 : 0>(a, s);
         else launch_scanm_i<M, 1, NBUF, false, 0, M == 8 ? 2 : 0>(a, s);
     } else if (a.k <= 64) VLQ_SM(1);

@@ -177,8 +177,7 @@ void launch_scanm_short(const ScanArgs& a_in, hipStream_t s) {
     if (a_in.nq <= 0) return;
     ScanArgs a = a_in;
     a.xcd_chunk = (int)((a.nq + 7) / 8);
-    static const bool keep_order = getenv("VLQ_SHORT_KEEP_ORDER") != nullptr;
-    a.short_keep_order = keep_order ? 1 : 0;
+    a.short_keep_order = 0;          // (multi-index cells by halves; the coarse-order walk was a retired A/B)
     switch (a.M) {
     case 4: launch_scanm_short_m<4>(a, s); break;
     case 8: launch_scanm_short_m<8>(a, s); break;
