@@ -447,18 +447,21 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
     if (h->imi_nbits > 0 && table_mode == 0)
         return fail(VLQ_ERR_UNSUPPORTED, "multi-index coarse quantizer without the precomputed table (type 2) is not built");
     const int64_t page = 32768;
-    // M=16 x 8 bit x d=128 in table mode 1: the scan kernel builds the per-query table itself
-    // (and the 8 / 32 / 64-byte kernels of scanm.hip, any dsub, when they will serve the batch)
-    const bool scanm_shape = table_mode == 1 && (h->M == 4 || h->M == 8 || h->M == 12 || (h->M >= 20 && h->M <= 32 && h->M % 4 == 0 && h->M != 16) ||
-                                                 (h->M >= 40 && h->M <= 64 && h->M % 8 == 0)) && h->ksub == 256 &&
-                             h->ntotal >= (int64_t)h->nlist * 24 && !env.generic_scan;
-    const bool fused_tables = (table_mode == 1 && h->M == 16 && h->ksub == 256 && h->dsub == 8) || scanm_shape;
-    if (table_mode != 0 && !fused_tables)
-        TRY(h->ws_qtab.reserve((size_t)std::min(n, page) * E * sizeof(float)));
+    vlq::ScanShape shape;
+    shape.M = h->M; shape.ksub = h->ksub; shape.dsub = h->dsub; shape.d = h->d; shape.nlist = h->nlist; shape.ntotal = h->ntotal;
+    shape.imi_nbits = h->imi_nbits; shape.table_mode = table_mode; shape.fp16_tables = h->fp16_tables; shape.have_rank = h->have_rank;
+    shape.scan_schedule = h->scan_schedule; shape.max_codes = h->max_codes;
+    shape.n = n; shape.nprobe = nprobe; shape.k = k;
+    shape.walk_first = env.walk_first; shape.scan16_variant = env.scan16_variant; shape.generic_scan = env.generic_scan;
     for (int64_t i0 = 0; i0 < n; i0 += page) {
         const int64_t ni = std::min(page, n - i0);
         const float* xi = x_dev + i0 * h->d;
-        if (table_mode != 0 && !fused_tables) {
+        shape.ni = ni;
+        const vlq::ScanPlan plan = vlq::plan_scan(shape);       // every decision about this page's launch (scan_plan.h)
+        const vlq::ScanLaunch& L = plan.launch;
+        const bool page_tables = table_mode != 0 && !plan.fused_tables;
+        if (page_tables) {
+            TRY(h->ws_qtab.reserve((size_t)ni * E * sizeof(float)));      // (the first page is the largest)
             StageTimer tm(h, 1);
             // init_query_L2 (IndexIVFPQ.cpp:557-563): ip table (mode 1) or distance table
             vlq::launch_pq_tables(xi, ni, h->d, h->pq.as<float>(), h->M, h->ksub, h->dsub, nullptr,
@@ -471,7 +474,7 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         a.list_off = h->list_off.as<int64_t>();
         a.list_len = h->list_len.as<int64_t>();
         a.term2 = table_mode == 1 ? h->term2.as<float>() : nullptr;
-        a.qtab = (table_mode != 0 && !fused_tables) ? h->ws_qtab.as<float>() : nullptr;
+        a.qtab = page_tables ? h->ws_qtab.as<float>() : nullptr;
         a.queries = xi;
         a.coarse = h->coarse.as<float>();
         a.pq_cent = h->pq.as<float>();
@@ -489,76 +492,71 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         a.imi_nbits = h->imi_nbits;
         a.max_codes = h->max_codes;
         a.store_pairs = store_pairs;
-        // walking order of a query's probes (walk_order.cuh; speed only): the nearest probe first, the rest in list-id order
-        // for the batches whose workgroups compete for the fabric -- k <= 64 (longer selections pay more for the late
-        // admission bound than the rows save: k = 100 0.81 -> 0.84 ms), nprobe >= 16, 8- (two-wave shape, from 3000 queries on:
-        // 0.366 -> 0.343 ms on the headline data, 2.15 -> 1.70 GB fetched; four waves 0.356 -> 0.359), every engineered size from
-        // 12 to 56 bytes (12 / 20 / 24 / 28 / 40 / 48 / 56 bytes: 0.53 / 0.92 / 1.14 / 1.37 / 1.96 / 2.37 / 2.80 -> 0.47 / 0.82 /
-        // 1.00 / 1.23 / 1.78 / 2.13 / 2.55 ms forced, more with the measured clock period; 64-byte codes 3.61 -> 3.47), and only when the batch's
-        // neighbours share few lists
-        // (walk_stat_kernel below).  VLQ_WALK_FIRST = n forces n probes in front for every batch, -1 the reference's order.
-        const bool walk_base = table_mode == 1 && h->imi_nbits == 0 &&
-                               ((h->M >= 12 && h->M <= 64 && h->M % 4 == 0) || (h->M == 8 && ni >= 3000)) &&
-                               h->ksub == 256 && ni >= 1024 && !h->fp16_tables;
-        // k <= 64 from 16 probes on; 64 < k <= 128 from 64 probes on with the 4 nearest in front (headline data, nprobe 64,
-        // k 100: 1.51 -> 1.38 ms; at nprobe 32 nothing to gain: 0.81 = 0.81) on indexes of short lists
-        const int walk_rule = !walk_base ? -1 : (k <= 64 && nprobe >= 16) ? 1
-                            : (k <= 128 && nprobe >= 64 && h->ntotal < (int64_t)h->nlist * 1024) ? 4 : -1;
-        a.walk_first = env.walk_first >= -1 ? env.walk_first : walk_rule;
-        {
-            a.walk_clock = env.walk_clock > 0 ? env.walk_clock : 0;
-            if (env.walk_clock == 0 && a.walk_first >= 0) {
-                // the workgroups' own walk times, per XCD; a new (nprobe, k, batch class) starts measuring afresh
-                if (!h->walk_state.p) { TRY(h->walk_state.reserve(8 * 16 * sizeof(int))); h->walk_key = -1; }
-                const int64_t wkey = ((int64_t)nprobe << 32) ^ ((int64_t)k << 16) ^ (int64_t)(ni >= 4096 ? 2 : 1);
-                if (wkey != h->walk_key) { (void)hipMemsetAsync(h->walk_state.p, 0, 8 * 16 * sizeof(int), h->stream); h->walk_key = wkey; h->walk_stat_calls = 0; }
-                a.walk_state = h->walk_state.as<int>();
-            }
+        a.long_lists = plan.long_lists;
+        a.nsplit = L.nsplit; a.tail_r = L.tail_r; a.tail_p = L.tail_p;
+        a.xcd_chunk = L.xcd_chunk; a.grid_per_xcd = L.grid_per_xcd;
+        a.walk_first = plan.walk_first;
+        a.walk_clock = env.walk_clock > 0 ? env.walk_clock : 0;
+        if (env.walk_clock == 0 && a.walk_first >= 0) {
+            // the workgroups' own walk times, per XCD; a new (nprobe, k, batch class) starts measuring afresh
+            if (!h->walk_state.p) { TRY(h->walk_state.reserve(8 * 16 * sizeof(int))); h->walk_key = -1; }
+            const int64_t wkey = ((int64_t)nprobe << 32) ^ ((int64_t)k << 16) ^ (int64_t)plan.walk_class;
+            if (wkey != h->walk_key) { (void)hipMemsetAsync(h->walk_state.p, 0, 8 * 16 * sizeof(int), h->stream); h->walk_key = wkey; h->walk_stat_calls = 0; }
+            a.walk_state = h->walk_state.as<int>();
         }
         // the statistic is computed with the scan order (launch_query_order); behind the order's ni entries: its 32 counts
-        const bool walk_auto = env.walk_first < -1 && a.walk_first >= 0;
         // (the counts live in the handle: the statistic describes the workload, not one batch -- it is sampled on the first
         // four searches of a (nprobe, k, batch class) and on every 16th after that, 6.4 us + a launch gap otherwise saved per
         // search.  Speed only: the results do not depend on the walking order)
+        const bool walk_auto = plan.walk_auto;
         if (walk_auto) TRY(h->walk_counts.reserve(32 * sizeof(int)));
         const bool walk_stat_now = walk_auto && (h->walk_stat_calls < 4 || h->walk_stat_calls % 16 == 0);
         if (walk_auto) h->walk_stat_calls++;
-        auto walk_part = [&]() -> int* { return walk_auto ? h->walk_counts.as<int>() : nullptr; };
-        // a launch with no measured walk time seeds its clock period from a model (walk_stat_kernel): the workgroups that will
-        // share the chip = the scan kernels' slots (scan16.hip: 2048 two-wave / 1280 four-wave workgroups), at most the batch
-        vlq::WalkSeed wseed;
-        wseed.list_off = h->list_off.as<int64_t>(); wseed.list_len = h->list_len.as<int64_t>(); wseed.nlist = h->nlist;
-        wseed.slots = (int)std::min<int64_t>(ni, (k <= 128 && ni >= 3000 && h->ntotal < (int64_t)h->nlist * 1024) ? 2048 : (k <= 64 ? 1280 : 1024));
-        // run queries that share their nearest centroid next to each other (L2 reuse), take the walk statistic along and
-        // decide the walking order from it; booked with the table stage
+        // the scan order of the queries (and, QueryOrder::walk, the walk statistic and the decision of the walking order from
+        // it); booked with the table stage -- the caller holds its StageTimer
         auto order_queries = [&]() -> int {
-            if (ni < 1024 || h->nlist > (1 << 22)) return VLQ_OK;
-            StageTimer tq(h, 1);
+            if (plan.order == vlq::QueryOrder::none) return VLQ_OK;
             TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
             TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
-            vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream,
-                                    (h->have_rank && h->imi_nbits == 0) ? h->list_rank.as<int>() : nullptr, walk_part(), a.walk_state, wseed, walk_stat_now, h->order_hist_ready && ni == n);
-            a.qorder = h->ws_qorder.as<int>();
-            if (walk_auto) {
-                const int samples = vlq::walk_stat_samples(ni, nprobe);
-                // from 128 probes on the list-id order won on both data sets (G1 2.26 -> 1.97 ms, headline 3.02 -> 2.48)
-                a.walk_limit = (int)((int64_t)samples * ((nprobe >= 128 && k <= 64) ? 1000 : env.walk_share) / 1000);
-                a.walk_flag = walk_part();
+            const int* rank = plan.order_by_rank ? h->list_rank.as<int>() : nullptr;
+            if (plan.order == vlq::QueryOrder::plain) {
+                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank);
+            } else {
+                vlq::WalkSeed wseed;
+                wseed.list_off = h->list_off.as<int64_t>(); wseed.list_len = h->list_len.as<int64_t>(); wseed.nlist = h->nlist;
+                wseed.slots = plan.walk_seed_slots;
+                int* counts = walk_auto ? h->walk_counts.as<int>() : nullptr;
+                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank,
+                                        counts, a.walk_state, wseed, walk_stat_now, h->order_hist_ready && plan.order_hist_ready);
+                if (walk_auto) {
+                    const int samples = vlq::walk_stat_samples(ni, nprobe);
+                    a.walk_limit = (int)((int64_t)samples * (plan.walk_limit_full ? 1000 : env.walk_share) / 1000);
+                    a.walk_flag = counts;
+                }
             }
+            a.qorder = h->ws_qorder.as<int>();
+            return VLQ_OK;
+        };
+        auto order_queries_timed = [&]() -> int {
+            if (plan.order == vlq::QueryOrder::none) return VLQ_OK;
+            StageTimer tq(h, 1);
+            TRY(order_queries());
             tq.stop();
             return VLQ_OK;
         };
         // what the page's scan launch was (vlq_ivfpq_last_scan_info); walked: the scan took a's walking order
-        auto record_scan = [&](const char* shape, bool walked) {
-            snprintf(h->last_scan, sizeof(h->last_scan), "%s", shape);
+        auto record_scan = [&](const char* name, bool walked) {
+            snprintf(h->last_scan, sizeof(h->last_scan), "%s", name);
             h->last_walk_first = walked ? a.walk_first : -1;
             h->last_walk_limit = walked ? a.walk_limit : 0;
             h->last_walk_samples = walked && a.walk_flag ? vlq::walk_stat_samples(ni, nprobe) : 0;
             h->last_walk_counts = walked && a.walk_flag != nullptr;   // (the 32 counts the order was decided from live in the handle)
         };
-        const bool fast16 = table_mode == 1 && h->M == 16 && h->ksub == 256;
-        if (h->fp16_tables && fast16 && h->imi_nbits == 0 && k <= 256) {
-            // useFloat16LookupTables: half(term 2) once per trained state, half(term 3) per page, half table sums
+        // a launcher refuses a plan whose kernel shape it has not built (plan_scan names none: tests/test_scan_plan.py)
+        auto built = [](bool ok) -> int { return ok ? VLQ_OK : fail(VLQ_ERR_HIP, "internal: the scan plan names a kernel shape that is not built"); };
+        char name[32];
+        switch (plan.path) {
+        case vlq::ScanPath::fp16: {
             TRY(ensure_term2h(h));
             TRY(h->ws_qtab.reserve((size_t)ni * E * sizeof(float)));
             TRY(h->ws_qtabh.reserve((size_t)ni * E * 2));
@@ -567,182 +565,151 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
                 vlq::launch_pq_tables(xi, ni, h->d, h->pq.as<float>(), h->M, h->ksub, h->dsub, nullptr, 0,
                                       h->ws_qtab.as<float>(), h->stream);
                 vlq::launch_to_half(h->ws_qtab.as<float>(), ni * (int64_t)E, -2.f, h->ws_qtabh.as<uint16_t>(), h->stream);
-                if (ni >= 1024) {
-                    TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
-                    TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
-                    vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream,
-                                            h->have_rank ? h->list_rank.as<int>() : nullptr);
-                    a.qorder = h->ws_qorder.as<int>();
-                }
+                TRY(order_queries());
                 tq.stop();
             }
             a.term2h = h->term2h.as<uint16_t>();
             a.qtabh = h->ws_qtabh.as<uint16_t>();
             StageTimer tm(h, 2);
-            vlq::launch_scan16h(a, h->stream);
+            TRY(built(vlq::launch_scan16h(a, L, h->stream)));
             tm.stop();
-            continue;
+            break;
         }
-        a.long_lists = h->ntotal >= (int64_t)h->nlist * 1024;   // mean list >= 4 chunks of 256 codes
-        if (fast16) {
-            // scan schedule (speed only): list-owned = one workgroup per (query, list partition), XCD x
-            // serves the lists of partition x, so their term2 rows and codes stay in that XCD's L2
-            const int sched = h->scan_schedule ? h->scan_schedule : 1;     // 0 = automatic = query-major (the faster one on every data set measured)
-            const bool owned = sched >= 2 && h->imi_nbits == 0 && h->have_rank && h->nlist >= 64 && h->nlist <= 16384 &&
-                               ni >= 1024 && nprobe >= 8 && h->dsub == 8 && h->ntotal >= (int64_t)h->nlist * 24;
-            if (owned) {
-                TRY(h->ws_own_hist.reserve(vlq::owned_hist_ints(h->nlist) * sizeof(int)));
-                TRY(h->ws_own_minr.reserve((size_t)ni * 8 * sizeof(int)));
-                TRY(h->ws_own_order.reserve((size_t)ni * 8 * sizeof(int)));
-                TRY(h->ws_own_count.reserve(64));
-                TRY(h->ws_part_mask.reserve((size_t)ni + 16));
-                TRY(h->ws_part_keys.reserve((size_t)ni * 8 * k * 8));
-                TRY(h->ws_qtab.reserve((size_t)ni * E * sizeof(float)));
-                if (sched >= 3 && vlq::scan16o_supports(a)) {         // second build: per-probe records, 8-byte item entries
-                    TRY(h->ws_own_recs.reserve((size_t)ni * nprobe * sizeof(vlq::OwnRec)));
-                    TRY(h->ws_own_seg.reserve((size_t)ni * 8 * 4));
-                    TRY(h->ws_own_items.reserve((size_t)ni * 8 * 8));
-                    vlq::ScanArgs ao = a;
-                    ao.qorder = nullptr;
-                    ao.qtab = h->ws_qtab.as<float>();
-                    ao.qtab_scaled = 1;
-                    ao.list_part = h->list_part.as<uint8_t>();
-                    ao.own_count = h->ws_own_count.as<int>();
-                    ao.part_mask = h->ws_part_mask.as<uint8_t>();
-                    ao.part_keys = h->ws_part_keys.as<unsigned long long>();
-                    ao.own_recs = h->ws_own_recs.as<vlq::OwnRec>();
-                    ao.own_items = h->ws_own_items.as<uint2>();
-                    {
-                        StageTimer tq(h, 1);
-                        vlq::launch_owned2_prepare(ao, h->list_rank.as<int>(), h->ws_own_hist.as<int>(), h->ws_own_minr.as<int>(),
-                                                   h->ws_own_seg.as<uint32_t>(), h->ws_own_items.as<uint2>(), h->ws_own_count.as<int>(),
-                                                   h->ws_part_mask.as<uint8_t>(), h->ws_own_recs.as<vlq::OwnRec>(), h->stream);
-                        vlq::launch_qtab16(xi, ni, h->pq_t.as<float>(), h->ws_qtab.as<float>(), h->stream);
-                        tq.stop();
-                    }
-                    if (getenv("VLQ_PHASE_TIMING")) {      // diagnostic: items per partition
-                        static int once = 0;
-                        if (!once++) {
-                            int cnt[8];
-                            (void)hipStreamSynchronize(h->stream);
-                            (void)hipMemcpy(cnt, h->ws_own_count.p, 32, hipMemcpyDeviceToHost);
-                            fprintf(stderr, "[owned] items per partition: %d %d %d %d %d %d %d %d\n", cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7]);
-                        }
-                    }
-                    StageTimer tm(h, 2);
-                    vlq::launch_scan16_owned2(ao, sched == 4 ? 2 : 1, h->stream);
-                    vlq::launch_owned_merge(ao, h->stream);
-                    tm.stop();
-                    continue;
-                }
-                {
-                    StageTimer tq(h, 1);   // item ordering + per-query tables are booked with the table stage
+        case vlq::ScanPath::owned:
+        case vlq::ScanPath::owned2: {
+            const bool second = plan.path == vlq::ScanPath::owned2;   // per-probe records, 8-byte item entries
+            TRY(h->ws_own_hist.reserve(vlq::owned_hist_ints(h->nlist) * sizeof(int)));
+            TRY(h->ws_own_minr.reserve((size_t)ni * 8 * sizeof(int)));
+            TRY(h->ws_own_order.reserve((size_t)ni * 8 * sizeof(int)));
+            TRY(h->ws_own_count.reserve(64));
+            TRY(h->ws_part_mask.reserve((size_t)ni + 16));
+            TRY(h->ws_part_keys.reserve((size_t)ni * 8 * k * 8));
+            TRY(h->ws_qtab.reserve((size_t)ni * E * sizeof(float)));
+            if (second) {
+                TRY(h->ws_own_recs.reserve((size_t)ni * nprobe * sizeof(vlq::OwnRec)));
+                TRY(h->ws_own_seg.reserve((size_t)ni * 8 * 4));
+                TRY(h->ws_own_items.reserve((size_t)ni * 8 * 8));
+            }
+            a.qtab = h->ws_qtab.as<float>();
+            a.qtab_scaled = 1;
+            a.list_part = h->list_part.as<uint8_t>();
+            a.own_count = h->ws_own_count.as<int>();
+            a.part_mask = h->ws_part_mask.as<uint8_t>();
+            a.part_keys = h->ws_part_keys.as<unsigned long long>();
+            if (second) {
+                a.own_recs = h->ws_own_recs.as<vlq::OwnRec>();
+                a.own_items = h->ws_own_items.as<uint2>();
+            } else {
+                a.own_order = h->ws_own_order.as<int>();
+            }
+            {
+                StageTimer tq(h, 1);   // item ordering + per-query tables are booked with the table stage
+                if (second)
+                    vlq::launch_owned2_prepare(a, h->list_rank.as<int>(), h->ws_own_hist.as<int>(), h->ws_own_minr.as<int>(),
+                                               h->ws_own_seg.as<uint32_t>(), h->ws_own_items.as<uint2>(), h->ws_own_count.as<int>(),
+                                               h->ws_part_mask.as<uint8_t>(), h->ws_own_recs.as<vlq::OwnRec>(), h->stream);
+                else
                     vlq::launch_owned_order(a.keys, ni, nprobe, h->nlist, h->list_rank.as<int>(), h->list_part.as<uint8_t>(),
                                             h->ws_own_hist.as<int>(), h->ws_own_minr.as<int>(), h->ws_own_order.as<int>(),
                                             h->ws_own_count.as<int>(), h->ws_part_mask.as<uint8_t>(), h->stream);
-                    vlq::launch_qtab16(xi, ni, h->pq_t.as<float>(), h->ws_qtab.as<float>(), h->stream);
-                    tq.stop();
-                }
-                vlq::ScanArgs ao = a;
-                ao.qorder = nullptr;
-                ao.qtab = h->ws_qtab.as<float>();
-                ao.qtab_scaled = 1;
-                ao.list_part = h->list_part.as<uint8_t>();
-                ao.own_order = h->ws_own_order.as<int>();
-                ao.own_count = h->ws_own_count.as<int>();
-                ao.part_mask = h->ws_part_mask.as<uint8_t>();
-                ao.part_keys = h->ws_part_keys.as<unsigned long long>();
-                StageTimer tm(h, 2);   // the scan of the items + the join of a query's parts
-                vlq::launch_scan16_owned(ao, h->stream);
-                vlq::launch_owned_merge(ao, h->stream);
-                tm.stop();
-                continue;
+                vlq::launch_qtab16(xi, ni, h->pq_t.as<float>(), h->ws_qtab.as<float>(), h->stream);
+                tq.stop();
             }
-            TRY(order_queries());
+            if (second && env.phase_timing) {      // diagnostic: items per partition
+                static int once = 0;
+                if (!once++) {
+                    int cnt[8];
+                    (void)hipStreamSynchronize(h->stream);
+                    (void)hipMemcpy(cnt, h->ws_own_count.p, 32, hipMemcpyDeviceToHost);
+                    fprintf(stderr, "[owned] items per partition: %d %d %d %d %d %d %d %d\n", cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7]);
+                }
+            }
+            StageTimer tm(h, 2);   // the scan of the items + the join of a query's parts
+            if (second) TRY(built(vlq::launch_scan16_owned2(a, L, h->stream)));
+            else TRY(built(vlq::launch_scan16(a, L, h->stream)));
+            vlq::launch_owned_merge(a, h->stream);
+            tm.stop();
+            break;
+        }
+        case vlq::ScanPath::scan16_short: {
+            TRY(order_queries_timed());
             StageTimer tm(h, 2);       // exactly the scan kernel
-            if (h->ntotal < (int64_t)h->nlist * 24) {       // a few codes per list
-                vlq::launch_scan16_short(a, h->stream);
-            }
-            else {
-                // fewer workgroups than the chip holds (256 CUs x 4): split every query's probes over
-                // several workgroups and join the partial rows -- serving-size batches
-                // (mid-size batches -- 1250 / 2500 queries, the slices of a batch sharded over 8 / 4 GPUs, which
-                // fill the 1024 slots a fractional number of times -- were tried with 2-8 parts too: a workgroup
-                // costs about 19 us of slot time before and after its probes against 1.5 us per probe, so the
-                // finer granularity buys nothing: 625 queries 0.090 -> 0.123 ms split in 8, 1250 queries 0.16 ms
-                // either way; tools/slice_stages.py)
-                int nsplit = 1;
-                while (k <= 256 && nsplit < 8 && ni * nsplit * 2 <= 1024 && nprobe / (nsplit * 2) >= 4) nsplit *= 2;
-                if (nsplit > 1) {
-                    TRY(h->ws_Dp.reserve((size_t)nsplit * ni * k * sizeof(float)));
-                    TRY(h->ws_Ip.reserve((size_t)nsplit * ni * k * sizeof(int64_t)));
-                    vlq::ScanArgs ap = a;
-                    ap.nsplit = nsplit;
-                    ap.D = h->ws_Dp.as<float>();
-                    ap.I = h->ws_Ip.as<int64_t>();
-                    vlq::launch_scan16(ap, h->stream);
-                    vlq::launch_merge_topk(ap.D, ap.I, ni, k, nsplit, a.D, a.I, h->stream);
-                } else if (k > 256 || (k > 128 && !a.long_lists)) {
-                    // one selection per workgroup.  128 < k <= 256 (round 3, 10 000 queries): bench index (lists of ~700
-                    // codes where probed) k = 200 1.06 -> 0.89 ms, k = 256 1.14 -> 0.90 ms against the per-wave lists of
-                    // scan16_kernel<4>; lists of 3 906 codes 4.01 / 4.14 ms for the pipelined scan16 against 4.56 / 4.59:
-                    // the trip barriers of the shared queue cost more than four private merge networks there
-                    vlq::launch_scan16_bigk(a, h->stream);
-                } else {
-                    // A batch that fills the chip's 4 x #CU workgroup slots a fractional number of times leaves most of the
-                    // chip idle in its last round (1250 queries, the slice of a 10 000-query batch on one of 8 GPUs: 1024 +
-                    // 226): the queries of that last round are split into parts (kernels.h: tail_r / tail_p), so that it is a
-                    // round of SHORT workgroups.  Measured (scan stage, G1 / headline data): 1100 queries 0.118 -> 0.103 / 0.139 ->
-                    // 0.125 ms, 1250 queries 0.122 -> 0.118 / 0.146 -> 0.133; from the third round on (2500 queries) it no longer
-                    // pays -- workgroups of an under-filled chip run faster as it is -- so only the second round is split
-                    const int64_t slots = (k <= 64 && !a.long_lists && h->imi_nbits == 0) ? 1280 : 1024;   // workgroups the chip holds (scan16.hip)
-                    const int64_t rem = ni % slots;
-                    int tp = rem > 0 ? (int)std::min<int64_t>(8, slots / rem) : 1;
-                    tp = std::min(tp, nprobe / 4);
-                    if (ni > slots && ni < 2 * slots && tp >= 2 && k <= 128) {
-                        vlq::ScanArgs at = a;
-                        at.tail_r = (int)((rem + 7) / 8);
-                        at.tail_p = tp;
-                        const size_t rows = (size_t)8 * at.tail_r;
-                        TRY(h->ws_Dp.reserve((size_t)tp * rows * k * sizeof(float)));
-                        TRY(h->ws_Ip.reserve((size_t)tp * rows * k * sizeof(int64_t)));
-                        TRY(h->ws_misc.reserve(rows * sizeof(int)));
-                        HIP_TRY(hipMemsetAsync(h->ws_misc.p, 0xFF, rows * sizeof(int), h->stream));
-                        at.tail_D = h->ws_Dp.as<float>();
-                        at.tail_I = h->ws_Ip.as<int64_t>();
-                        at.tail_rows = h->ws_misc.as<int>();
-                        vlq::launch_scan16(at, h->stream);
-                        vlq::launch_merge_topk(at.tail_D, at.tail_I, (int64_t)rows, k, tp, a.D, a.I, h->stream, at.tail_rows);
-                    } else {
-                        vlq::launch_scan16(a, h->stream);
-                    }
-                }
-            }
+            TRY(built(vlq::launch_scan16_short(a, L, h->stream)));
             tm.stop();
-            record_scan(h->ntotal >= (int64_t)h->nlist * 24 ? vlq::last_scan16_shape() : "scan16_short_kernel", true);
-        } else if ((vlq::scanm_supports(a) || vlq::scanm0_supports(a)) && h->ntotal >= (int64_t)h->nlist * 24 && !env.generic_scan) {
-            // 8 / 32 / 64-byte codes: the engineered organisation (scanm.hip); queries ordered like the 16-byte path
-            TRY(order_queries());
+            record_scan("scan16_short_kernel", true);
+            break;
+        }
+        case vlq::ScanPath::scan16_split: {
+            TRY(order_queries_timed());
             StageTimer tm(h, 2);
-            vlq::launch_scanm(a, h->stream);
+            TRY(h->ws_Dp.reserve((size_t)L.nsplit * ni * k * sizeof(float)));
+            TRY(h->ws_Ip.reserve((size_t)L.nsplit * ni * k * sizeof(int64_t)));
+            vlq::ScanArgs ap = a;
+            ap.D = h->ws_Dp.as<float>();
+            ap.I = h->ws_Ip.as<int64_t>();
+            TRY(built(vlq::launch_scan16(ap, L, h->stream)));
+            vlq::launch_merge_topk(ap.D, ap.I, ni, k, L.nsplit, a.D, a.I, h->stream);
             tm.stop();
-            char shape[32];
-            snprintf(shape, sizeof(shape), "scanm_kernel<%d>", h->M);
-            record_scan(shape, true);
-        } else if (h->M != 16 && h->ntotal < (int64_t)h->nlist * 24 && vlq::scanm_short_supports(a) && !env.generic_scan) {
-            // a few codes per list, any engineered code size but 16 bytes (the multi-index drivers ship 8): no table per probe,
-            // each lane fetches the entries its code addresses (scanm_short.hip)
+            record_scan(vlq::last_scan16_shape(), true);
+            break;
+        }
+        case vlq::ScanPath::scan16_bigk: {
+            TRY(order_queries_timed());
             StageTimer tm(h, 2);
-            vlq::launch_scanm_short(a, h->stream);
+            TRY(built(vlq::launch_scan16_bigk(a, L, h->stream)));
             tm.stop();
-            char shape[32];
-            snprintf(shape, sizeof(shape), "scanm_short_kernel<%d>", h->M);
-            record_scan(shape, false);
-        } else {
+            record_scan(vlq::last_scan16_shape(), true);      // (as ever: the thread's last scan16_kernel launch -- this launcher leaves no name)
+            break;
+        }
+        case vlq::ScanPath::scan16_tail: {
+            TRY(order_queries_timed());
+            StageTimer tm(h, 2);
+            const size_t rows = (size_t)8 * L.tail_r;
+            TRY(h->ws_Dp.reserve((size_t)L.tail_p * rows * k * sizeof(float)));
+            TRY(h->ws_Ip.reserve((size_t)L.tail_p * rows * k * sizeof(int64_t)));
+            TRY(h->ws_misc.reserve(rows * sizeof(int)));
+            HIP_TRY(hipMemsetAsync(h->ws_misc.p, 0xFF, rows * sizeof(int), h->stream));
+            a.tail_D = h->ws_Dp.as<float>();
+            a.tail_I = h->ws_Ip.as<int64_t>();
+            a.tail_rows = h->ws_misc.as<int>();
+            TRY(built(vlq::launch_scan16(a, L, h->stream)));
+            vlq::launch_merge_topk(a.tail_D, a.tail_I, (int64_t)rows, k, L.tail_p, a.D, a.I, h->stream, a.tail_rows);
+            tm.stop();
+            record_scan(vlq::last_scan16_shape(), true);
+            break;
+        }
+        case vlq::ScanPath::scan16: {
+            TRY(order_queries_timed());
+            StageTimer tm(h, 2);
+            TRY(built(vlq::launch_scan16(a, L, h->stream)));
+            tm.stop();
+            record_scan(vlq::last_scan16_shape(), true);
+            break;
+        }
+        case vlq::ScanPath::scanm: {
+            TRY(order_queries_timed());
+            StageTimer tm(h, 2);
+            TRY(built(vlq::launch_scanm(a, L, h->stream)));
+            tm.stop();
+            snprintf(name, sizeof(name), "scanm_kernel<%d>", h->M);
+            record_scan(name, true);
+            break;
+        }
+        case vlq::ScanPath::scanm_short: {
+            StageTimer tm(h, 2);
+            TRY(built(vlq::launch_scanm_short(a, L, h->stream)));
+            tm.stop();
+            snprintf(name, sizeof(name), "scanm_short_kernel<%d>", h->M);
+            record_scan(name, false);
+            break;
+        }
+        case vlq::ScanPath::generic: {
             StageTimer tm(h, 2);
             vlq::launch_scan(a, h->stream);
             tm.stop();
             record_scan("scan_kernel", false);
+            break;
+        }
         }
     }
     HIP_TRY(hipGetLastError());

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "scan_plan.h"
+
 namespace vlq {
 
 // The library's run-time switches, read once per process.  None changes a result: each pins a path that a test or a
@@ -135,7 +137,7 @@ struct OwnRec {
     float dis0;       // coarse distance
     uint32_t pos0;    // scan position of the list's first code (prefix over the query's probes in coarse order)
 };
-static_assert(sizeof(OwnRec) == 24, "OwnRec is copied as six dwords");
+static_assert(sizeof(OwnRec) == kOwnRecBytes, "OwnRec is copied as six dwords");
 
 struct ScanArgs {
     const uint8_t* codes;        // [ntotal][M] list-contiguous
@@ -171,7 +173,7 @@ struct ScanArgs {
     float* tail_D = nullptr;
     int64_t* tail_I = nullptr;
     int* tail_rows = nullptr;    // [8 * tail_r], preset to -1
-    int xcd_chunk = 0;           // set by the launcher
+    int xcd_chunk = 0;           // from the plan (ScanLaunch)
     const int* walk_flag = nullptr;  // optional: walk_stat_kernel's 32 counts of probes shared by neighbours of the scan order ...
     int walk_clock = 0;              // A/B: fixed period of the walk clock in 10 ns ticks (VLQ_WALK_CLOCK)
     int* walk_state = nullptr;       // per XCD (16 ints apart): running mean of a workgroup's walk time, kept across launches
@@ -179,7 +181,7 @@ struct ScanArgs {
     int walk_limit = 0;              // ... list-id order only while their sum is <= this
     int short_keep_order = 0;    // scan16_short: walk a query's multi-index cells in coarse order instead of by halves (retired A/B: always 0)
     int walk_first = -1;         // walk_order.cuh: < 0 = probes in coarse-distance order, else this many nearest first, the rest by list id
-    int grid_per_xcd = 0;        // set by the launcher: workgroups per XCD (xcd_chunk unless the tail is split)
+    int grid_per_xcd = 0;        // from the plan: workgroups per XCD (xcd_chunk unless the tail is split)
     // list-owned schedule (scan16 only, DESIGN.md "list-owned schedule"): the lists are cut into 8
     // partitions of neighbouring lists, one per XCD; a workgroup serves the probes of ONE query that fall
     // into ONE partition and leaves its k best raw keys (ordered distance << 32 | scan position) in
@@ -199,43 +201,40 @@ struct ScanArgs {
     const uint16_t* qtabh = nullptr;
 };
 void launch_scan(const ScanArgs& a, hipStream_t s);
-// 8-, 32- and 64-byte codes (M x 8 bit), table mode 1 / table type 2, per-query table in a.qtab: scan16's organisation over the
-// code size (scanm.hip); same results as launch_scan
-bool scanm_supports(const ScanArgs& a);
-bool scanm0_supports(const ScanArgs& a);      // table mode 0, 8- / 16-byte codes (launch_scanm serves it too)
-void launch_scanm(const ScanArgs& a, hipStream_t s);
+// The engineered scan kernels.  Which of them serves a page, in which instantiation and with how much LDS is plan_scan's
+// decision (scan_plan.h); a launcher takes the plan's ScanLaunch -- the caller has copied its nsplit / tail_r / tail_p /
+// xcd_chunk / grid_per_xcd into the ScanArgs -- and returns false for a shape that is not built.  Same results as launch_scan.
+// 8-, 32- and 64-byte codes (M x 8 bit), table mode 1 / table type 2, per-query table in a.qtab, and table mode 0 for 8- / 16- /
+// 32-byte codes: scan16's organisation over the code size (scanm.hip)
+bool launch_scanm(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // specialisation for M = 16, ksub = 256, table_mode = 1 (scan16.hip)
-void launch_scan16(const ScanArgs& a, hipStream_t s);
+bool launch_scan16(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 const char* last_scan16_shape();      // "scan16_kernel<KPL, NW, NBUF, PIPE, IMI, OWNED>" of this thread's last launch
-// list-owned schedule of the same kernel: launch_owned_order prepares own_order / own_count / part_mask,
-// launch_qtab16 the per-query table (-2 <q_m, cent_mj>, [nq][16][256]), launch_scan16_owned scans the
+// list-owned schedule of the same kernel (L.owned): launch_owned_order prepares own_order / own_count / part_mask,
+// launch_qtab16 the per-query table (-2 <q_m, cent_mj>, [nq][16][256]), launch_scan16 scans the
 // (query, partition) items and launch_owned_merge writes the final rows
 void launch_owned_order(const int64_t* keys, int64_t nq, int nprobe, int nlist, const int* list_rank,
                         const uint8_t* list_part, int* hist /* [2][8][nlist] + 8 */, int* minr /* [nq][8] */,
                         int* own_order, int* own_count, uint8_t* part_mask, hipStream_t s);
 inline size_t owned_hist_ints(int nlist) { return (size_t)16 * nlist + 64; }
 void launch_qtab16(const float* queries, int64_t nq, const float* pq_cent_t, float* qtab, hipStream_t s);
-void launch_scan16_owned(const ScanArgs& a, hipStream_t s);
 void launch_owned_merge(const ScanArgs& a, hipStream_t s);
 // second build of the list-owned schedule (scan16o.hip): launch_owned2_prepare writes the per-probe records, the items of
 // every partition, own_count and part_mask (hist: [2][8][nlist] ints of scratch, minr [nq][8], seg [nq][8]);
-// launch_scan16_owned2 scans the items (nbuf = 1 / 2 table buffers); launch_owned_merge joins the parts as before
-bool scan16o_supports(const ScanArgs& a);
+// launch_scan16_owned2 scans the items (L.nbuf = 1 / 2 table buffers); launch_owned_merge joins the parts as before
 void launch_owned2_prepare(const ScanArgs& a, const int* list_rank, int* hist, int* minr, uint32_t* seg, uint2* items,
                            int* own_count, uint8_t* part_mask, OwnRec* recs, hipStream_t s);
-void launch_scan16_owned2(const ScanArgs& a, int nbuf, hipStream_t s);
+bool launch_scan16_owned2(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // same shape with float16 look-up tables (useFloat16LookupTables; scan16h.hip), k <= 256
-bool scan16h_supports(const ScanArgs& a);
-void launch_scan16h(const ScanArgs& a, hipStream_t s);
+bool launch_scan16h(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // *out = bit pattern of the largest |x[i]| (the half-range check of the float16 tables)
 void launch_max_abs(const float* x, int64_t n, unsigned int* out, hipStream_t s);
 // same shape, 256 < k <= 1024: one selection per workgroup instead of one per wave (scan16k.hip)
-void launch_scan16_bigk(const ScanArgs& a, hipStream_t s);
+bool launch_scan16_bigk(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // same shape, indexes with a few codes per list (multi-index): no per-probe LUT (scan16.hip)
-void launch_scan16_short(const ScanArgs& a, hipStream_t s);
+bool launch_scan16_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // the same organisation for the other code sizes (4 ... 64 bytes in the steps scanm.hip serves; per-query table in a.qtab)
-bool scanm_short_supports(const ScanArgs& a);
-void launch_scanm_short(const ScanArgs& a, hipStream_t s);
+bool launch_scanm_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this
 inline size_t query_order_bins_padded(int nlist) {

@@ -507,7 +507,7 @@ __global__ __launch_bounds__(256) void owned_merge_kernel(ScanArgs a, int stride
 
 void launch_owned_merge(const ScanArgs& a, hipStream_t s) {
     if (a.nq <= 0) return;
-    const int stride = (int)((512 + (size_t)a.nprobe * 24 + 8 + 15) & ~(size_t)15);
+    const int stride = (int)((512 + probe_meta_bytes(a.nprobe) + 15) & ~(size_t)15);
     const size_t smem = (size_t)4 * stride;
     dim3 grid((unsigned)((a.nq + 3) / 4)), block(256);
 #define VLQ_OM(K)                                                                                  \
@@ -762,18 +762,14 @@ static void launch_scan16_short_t(const ScanArgs& a, int queue_off, size_t smem,
     hipLaunchKernelGGL((scan16_short_kernel<KPL>), dim3(grid), dim3(256), smem, s, a, queue_off);
 }
 
-void launch_scan16_short(const ScanArgs& a_in, hipStream_t s) {
-    if (a_in.nq <= 0) return;
-    ScanArgs a = a_in;
-    a.xcd_chunk = (int)((a.nq + 7) / 8);
-    a.short_keep_order = 0;          // (multi-index cells by halves; the coarse-order walk was a retired A/B)
-    size_t region = (size_t)4096 * 4;                        // the merge area aliases the table
-    const size_t merge = (size_t)4 * a.k * 8;
-    if (region < merge) region = merge;
-    const size_t smem = region + (size_t)4 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 64;
-    if (a.k <= 64) launch_scan16_short_t<1>(a, (int)region, smem, s);
-    else if (a.k <= 256) launch_scan16_short_t<4>(a, (int)region, smem, s);
-    else launch_scan16_short_t<16>(a, (int)region, smem, s);
+bool launch_scan16_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
+    switch (L.kpl) {
+    case 1: launch_scan16_short_t<1>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 4: launch_scan16_short_t<4>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 16: launch_scan16_short_t<16>(a, L.lut_region, L.lds_bytes, s); return true;
+    }
+    return false;
 }
 
 template <int KPL, int NW, int NBUF, bool PIPE, bool IMI>
@@ -787,82 +783,32 @@ static thread_local char g_last_scan16[64] = "";
 const char* last_scan16_shape() { return g_last_scan16; }
 
 template <int KPL, int NW, int NBUF, bool PIPE>
-static void launch_scan16_t(const ScanArgs& a, int lut_region, size_t smem, hipStream_t s) {
+static void launch_scan16_t(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
     snprintf(g_last_scan16, sizeof(g_last_scan16), "scan16_kernel<%d, %d, %d, %s, %s, %s>", KPL, NW, NBUF, PIPE ? "true" : "false",
-             a.imi_nbits > 0 ? "true" : "false", a.part_keys ? "true" : "false");
-    if (a.part_keys) {        // list-owned schedule: 8 x nq slots, the surplus exits at once
-        ensure_dynamic_lds(reinterpret_cast<const void*>(scan16_kernel<KPL, NW, NBUF, PIPE, false, true>), smem);
-        hipLaunchKernelGGL((scan16_kernel<KPL, NW, NBUF, PIPE, false, true>), dim3((unsigned)(8 * a.nq)), dim3(64 * NW), smem, s,
-                           a, lut_region);
+             L.imi ? "true" : "false", L.owned ? "true" : "false");
+    if (L.owned) {        // list-owned schedule: 8 x nq slots, the surplus exits at once
+        ensure_dynamic_lds(reinterpret_cast<const void*>(scan16_kernel<KPL, NW, NBUF, PIPE, false, true>), L.lds_bytes);
+        hipLaunchKernelGGL((scan16_kernel<KPL, NW, NBUF, PIPE, false, true>), dim3((unsigned)(8 * a.nq)), dim3(64 * NW), L.lds_bytes, s,
+                           a, L.lut_region);
         return;
     }
-    if (a.imi_nbits > 0) launch_scan16_i<KPL, NW, NBUF, PIPE, true>(a, lut_region, smem, s);
-    else launch_scan16_i<KPL, NW, NBUF, PIPE, false>(a, lut_region, smem, s);
+    if (L.imi) launch_scan16_i<KPL, NW, NBUF, PIPE, true>(a, L.lut_region, L.lds_bytes, s);
+    else launch_scan16_i<KPL, NW, NBUF, PIPE, false>(a, L.lut_region, L.lds_bytes, s);
 }
 
-void launch_scan16_owned(const ScanArgs& a, hipStream_t s) { launch_scan16(a, s); }
-
-void launch_scan16(const ScanArgs& a_in, hipStream_t s) {
-    if (a_in.nq <= 0) return;
-    ScanArgs a = a_in;
-    if (a.nsplit < 1 || a.part_keys) a.nsplit = 1;
-    a.xcd_chunk = (int)((a.nq * a.nsplit + 7) / 8);
-    if (a.nsplit > 1 || a.part_keys || !a.tail_D) a.tail_r = 0;
-    a.grid_per_xcd = a.xcd_chunk;
-    if (a.tail_r > 0) {              // per XCD: its whole queries, then tail_p workgroups for each of its last tail_r
-        if (a.tail_r > a.xcd_chunk) a.tail_r = a.xcd_chunk;
-        a.grid_per_xcd = a.xcd_chunk - a.tail_r + a.tail_r * a.tail_p;
+// the instantiation plan_scan chose (scan_plan.h: the shapes and what was measured for each)
+bool launch_scan16(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
+#define VLQ_S16(KPL, NW, NBUF, PIPE)                                                                     \
+    if (L.kpl == KPL && L.nw == NW && L.nbuf == NBUF && L.pipe == PIPE) {                                \
+        launch_scan16_t<KPL, NW, NBUF, PIPE>(a, L, s);                                                               \
+        return true;                                                                                     \
     }
-    // k <= 64: 8 waves per workgroup share one LUT (32 waves per CU at 4 workgroups);
-    // larger k keeps more selection state per wave, so stay at 4 waves
-    // Measured alternatives (r01, MI355X, bench data): 8 waves per workgroup 0.95 ms, single
-    // LUT buffer with 6 workgroups per CU 0.78 ms, two probes of lookahead 0.82 ms, two
-    // queries per workgroup sharing term2 rows 0.93 ms -- against 0.78-0.82 ms for this
-    // configuration (4 waves, double-buffered LUT, one probe of lookahead).
-    // (r03, against 0.649 ms: single LUT buffer without the pair loop = 99 VGPRs = 5 workgroups per CU 0.682 ms, single
-    // buffer with the pair loop at 4 per CU 0.668 ms.)
-    const int nw = 4;
-    size_t lutb = (size_t)2 * 4096 * 4;
-    const size_t merge = (size_t)nw * a.k * 8;
-    if (lutb < merge) lutb = merge;
-    const size_t wrec = a.nprobe <= 64 ? (size_t)a.nprobe * 12 + 8 : 0;       // walking-order copies of the probe metadata (scan16_kernel)
-    const size_t tail = (size_t)nw * 64 * 8 * (a.k > 256 ? 4 : 1) + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64 + wrec;
-    const size_t smem = lutb + tail;
-    // k <= 64.  Lists of a few hundred codes (mean list < 1024 codes: every BASELINE shape but the long-list tools): ONE table
-    // buffer and the plain chunk loop -- 95 VGPRs and 19 KB of LDS = 5 workgroups per CU instead of 4.  Round 4, 10 000
-    // queries: G1 data 0.649 -> 0.606 ms (0.97 of the LDS gather rate), headline data 0.730 = 0.730 (row traffic bound); 2500
-    // queries 0.230 -> 0.215 / 0.192 -> 0.179 ms: 1280 slots hold a sharded batch's slice in fewer rounds.  Long lists keep two
-    // buffers and the pair loop (two chunks per trip, the adds of one under the gathers of the other).
-    const int variant = env().scan16_variant;
-    const bool plain = !a.part_keys && a.imi_nbits == 0;
-    // ... and from 3000 queries on TWO waves per workgroup (a thread owns 32 table entries: 127 VGPRs, 8 workgroups per CU = 2048
-    // slots): a list of 330 codes is 3 trips of 128 lanes instead of 2 trips of 256 -- 25 % fewer lane slots, and a two-wave
-    // barrier.  10 000 queries: headline data 0.604 -> 0.548 ms, nprobe 16 / 64 / 128 0.356 / 1.08 / 2.04 -> 0.327 / 0.99 / 1.92,
-    // k = 50 0.649 -> 0.563, G1 0.626 -> 0.595; below 3000 queries the 2048 slots of slower workgroups lose to 1280 (2500
-    // queries 0.183 -> 0.202, 1250 queries on G1 0.101 -> 0.116).  VLQ_SCAN16_VARIANT = 4 / 1 force two / four waves.
-    if (a.k <= 64 && plain && !a.tail_r && a.nsplit == 1 && (variant == 4 || (variant < 0 && !a.long_lists && a.nq >= 3000))) {
-        const size_t l1 = std::max((size_t)4096 * 4, (size_t)2 * a.k * 8);
-        const size_t tail2 = (size_t)2 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64 + wrec;
-        launch_scan16_t<1, 2, 1, false>(a, (int)l1, l1 + tail2, s);
-    } else if (a.k <= 64 && plain && (variant == 1 || (variant < 0 && !a.long_lists))) {
-        const size_t l1 = std::max((size_t)4096 * 4, merge);
-        launch_scan16_t<1, 4, 1, false>(a, (int)l1, l1 + tail, s);
-    } else if (a.k <= 64) launch_scan16_t<1, 4, 2, true>(a, (int)lutb, smem, s);
-    else if (a.k <= 128 && plain && !a.tail_r && a.nsplit == 1 && variant < 0 && !a.long_lists && a.nq >= 3000) {
-        // two waves per workgroup as for k <= 64 (128 VGPRs forced): k = 100, 10 000 queries: headline data 0.815 -> 0.77 ms,
-        // nprobe 64 1.34 -> 1.13, G1 0.75 -> 0.68
-        const size_t l1 = std::max((size_t)4096 * 4, (size_t)2 * a.k * 8);
-        const size_t tail2 = (size_t)2 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64 + wrec;
-        launch_scan16_t<2, 2, 1, false>(a, (int)l1, l1 + tail2, s);
-    }
-    else if (a.k <= 128) {          // recall@100: half the merge network of the 256-key list
-        if (a.long_lists) launch_scan16_t<2, 4, 2, true>(a, (int)lutb, smem, s);
-        else launch_scan16_t<2, 4, 2, false>(a, (int)lutb, smem, s);
-    } else if (a.k <= 256) {
-        if (a.long_lists) launch_scan16_t<4, 4, 2, true>(a, (int)lutb, smem, s);
-        else launch_scan16_t<4, 4, 2, false>(a, (int)lutb, smem, s);
-    } else if (a.k <= 512) launch_scan16_t<8, 4, 2, false>(a, (int)lutb, smem, s);
-    else launch_scan16_t<16, 4, 2, false>(a, (int)lutb, smem, s);
+    VLQ_S16(1, 2, 1, false) VLQ_S16(1, 4, 1, false) VLQ_S16(1, 4, 2, true) VLQ_S16(2, 2, 1, false)
+    VLQ_S16(2, 4, 2, true) VLQ_S16(2, 4, 2, false) VLQ_S16(4, 4, 2, true) VLQ_S16(4, 4, 2, false)
+    VLQ_S16(8, 4, 2, false) VLQ_S16(16, 4, 2, false)
+#undef VLQ_S16
+    return false;
 }
 
 // ---------------------------------------------------------------------------

@@ -308,7 +308,7 @@ struct ProbeMeta {
     uint32_t* plen;   // [nprobe]
     int32_t* pkey;    // [nprobe] list id, -1 = not visited (invalid key, empty list, behind max_codes)
     float* pd0;       // [nprobe] coarse distance
-    __device__ __forceinline__ static size_t bytes(int nprobe) { return (size_t)nprobe * 24 + 8; }
+    __device__ __forceinline__ static size_t bytes(int nprobe) { return probe_meta_bytes(nprobe); }      // (scan_plan.h: the launchers' LDS sizes count it too)
     __device__ __forceinline__ void carve(unsigned char* base, int nprobe) {
         poff = reinterpret_cast<int64_t*>(base);
         cum = reinterpret_cast<uint32_t*>(poff + nprobe);

@@ -175,25 +175,17 @@ __global__ __launch_bounds__(256) void scan16h_kernel(ScanArgs a, int lut_region
 template <int KPL>
 static void launch_scan16h_t(const ScanArgs& a, int lut_region, size_t smem, hipStream_t s) {
     ensure_dynamic_lds(reinterpret_cast<const void*>(scan16h_kernel<KPL>), smem);
-    const unsigned grid = (unsigned)(((a.nq + 7) / 8) * 8);
-    ScanArgs b = a;
-    b.xcd_chunk = (a.nq + 7) / 8;
-    hipLaunchKernelGGL((scan16h_kernel<KPL>), dim3(grid), dim3(256), smem, s, b, lut_region);
+    hipLaunchKernelGGL((scan16h_kernel<KPL>), dim3((unsigned)(8 * a.xcd_chunk)), dim3(256), smem, s, a, lut_region);
 }
 
-bool scan16h_supports(const ScanArgs& a) {
-    return a.M == 16 && a.ksub == 256 && a.table_mode == 1 && a.imi_nbits == 0 && a.k <= 256 && a.term2h && a.qtabh;
-}
-
-void launch_scan16h(const ScanArgs& a, hipStream_t s) {
-    if (a.nq <= 0) return;
-    size_t lutb = (size_t)2 * 8192;
-    const size_t merge = (size_t)4 * a.k * 8;
-    if (lutb < merge) lutb = merge;
-    const size_t smem = lutb + 4 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64;
-    if (a.k <= 64) launch_scan16h_t<1>(a, (int)lutb, smem, s);
-    else if (a.k <= 128) launch_scan16h_t<2>(a, (int)lutb, smem, s);
-    else launch_scan16h_t<4>(a, (int)lutb, smem, s);
+bool launch_scan16h(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
+    switch (L.kpl) {
+    case 1: launch_scan16h_t<1>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 2: launch_scan16h_t<2>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 4: launch_scan16h_t<4>(a, L.lut_region, L.lds_bytes, s); return true;
+    }
+    return false;
 }
 
 // largest |x[i]| (as the bit pattern of a non-negative float: orders like an integer)

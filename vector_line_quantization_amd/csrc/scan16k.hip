@@ -395,18 +395,21 @@ static void launch_bigk_t(const ScanArgs& a, int lut_region, size_t smem, hipStr
     hipLaunchKernelGGL((scan16_bigk_kernel<KC, IMI>), dim3((unsigned)(8 * a.xcd_chunk)), dim3(256), smem, s, a, lut_region);
 }
 
-void launch_scan16_bigk(const ScanArgs& a_in, hipStream_t s) {
-    if (a_in.nq <= 0) return;
-    ScanArgs a = a_in;
-    a.nsplit = 1;
-    a.xcd_chunk = (int)((a.nq + 7) / 8);
-    const int kc = a.k <= 256 ? 256 : a.k <= 512 ? 512 : 1024;
-    const size_t lutb = (size_t)4096 * 4;
-    const size_t smem = lutb + (size_t)(kc + kPendCap) * 8 + 3 * 256 * 4 + 64 * 8 + (size_t)a.nprobe * 24 + 8 + 104 + (size_t)a.nprobe * 2 + 64;
-    const bool imi = a.imi_nbits > 0;
-    if (kc == 256) { if (imi) launch_bigk_t<256, true>(a, (int)lutb, smem, s); else launch_bigk_t<256, false>(a, (int)lutb, smem, s); }
-    else if (kc == 512) { if (imi) launch_bigk_t<512, true>(a, (int)lutb, smem, s); else launch_bigk_t<512, false>(a, (int)lutb, smem, s); }
-    else { if (imi) launch_bigk_t<1024, true>(a, (int)lutb, smem, s); else launch_bigk_t<1024, false>(a, (int)lutb, smem, s); }
+static_assert(kPendCap == kBigkPending, "plan_scan sizes the LDS of this kernel");
+bool launch_scan16_bigk(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
+#define VLQ_BK(KC)                                                                  \
+    case KC:                                                                        \
+        if (L.imi) launch_bigk_t<KC, true>(a, L.lut_region, L.lds_bytes, s);        \
+        else launch_bigk_t<KC, false>(a, L.lut_region, L.lds_bytes, s);             \
+        return true
+    switch (L.kpl) {
+    VLQ_BK(256);
+    VLQ_BK(512);
+    VLQ_BK(1024);
+    }
+#undef VLQ_BK
+    return false;
 }
 
 }  // namespace vlq

@@ -282,28 +282,17 @@ __global__ __launch_bounds__(256) void scan16o_kernel(ScanArgs a, int lut_region
 }
 
 template <int KPL, int NBUF>
-static void launch_scan16o_t(const ScanArgs& a, hipStream_t s) {
-    size_t lutb = (size_t)NBUF * 4096 * 4;
-    const size_t merge = (size_t)4 * a.k * 8;
-    if (lutb < merge) lutb = merge;
-    const size_t smem = lutb + 4 * 64 * 8 + (size_t)a.nprobe * 24 + 16;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(scan16o_kernel<KPL, NBUF>), smem);
-    hipLaunchKernelGGL((scan16o_kernel<KPL, NBUF>), dim3((unsigned)(8 * a.nq)), dim3(256), smem, s, a, (int)lutb);
+static void launch_scan16o_t(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    ensure_dynamic_lds(reinterpret_cast<const void*>(scan16o_kernel<KPL, NBUF>), L.lds_bytes);
+    hipLaunchKernelGGL((scan16o_kernel<KPL, NBUF>), dim3((unsigned)(8 * a.nq)), dim3(256), L.lds_bytes, s, a, L.lut_region);
 }
 
-bool scan16o_supports(const ScanArgs& a) { return a.nprobe <= 64 && a.k <= 256 && a.M == 16 && a.ksub == 256; }
-
-void launch_scan16_owned2(const ScanArgs& a, int nbuf, hipStream_t s) {
-    if (a.nq <= 0) return;
-    if (nbuf == 2) {
-        if (a.k <= 64) launch_scan16o_t<1, 2>(a, s);
-        else if (a.k <= 128) launch_scan16o_t<2, 2>(a, s);
-        else launch_scan16o_t<4, 2>(a, s);
-    } else {
-        if (a.k <= 64) launch_scan16o_t<1, 1>(a, s);
-        else if (a.k <= 128) launch_scan16o_t<2, 1>(a, s);
-        else launch_scan16o_t<4, 1>(a, s);
-    }
+bool launch_scan16_owned2(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
+#define VLQ_SO(KPL, NBUF) if (L.kpl == KPL && L.nbuf == NBUF) { launch_scan16o_t<KPL, NBUF>(a, L, s); return true; }
+    VLQ_SO(1, 2) VLQ_SO(2, 2) VLQ_SO(4, 2) VLQ_SO(1, 1) VLQ_SO(2, 1) VLQ_SO(4, 1)
+#undef VLQ_SO
+    return false;
 }
 
 }  // namespace vlq

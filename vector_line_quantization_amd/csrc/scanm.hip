@@ -159,7 +159,7 @@ template <int M> struct ScanMShape {
     // VGPRs, one workgroup per CU either way; forcing 128 VGPRs for two workgroups spills: 4.41 / 3.81 (round 5, with the
     // chunks requested a probe ahead: 3.62 / 3.77 at one workgroup, 4.05 / 3.34 forced to two -- the headline data's 64 KB rows,
     // 21 GB requested per launch, are what bounds it: more workgroups in flight only lower the L2 hit rate).
-    static constexpr int NW = M <= 32 ? 4 : 8;
+    static constexpr int NW = scanm_waves(M);
     static constexpr int NT = 64 * NW;
     static constexpr int E = M * 256;
     static constexpr int NI = E / 4 / NT;                    // float4 of the table per thread: 2 (M = 8), 4, or 8 (M = 32, 64)
@@ -560,95 +560,73 @@ __global__ __launch_bounds__(64 * (NWX ? NWX : ScanMShape<M>::NW)) __attribute__
 }
 
 template <int M, int KPL, int NBUF, bool IMI, int DSUB = 0, int NWX = 0>
-static void launch_scanm_i(const ScanArgs& a, hipStream_t s) {
-    constexpr int NW = NWX ? NWX : ScanMShape<M>::NW, E = ScanMShape<M>::E;
-    size_t lutb = (size_t)NBUF * E * 4;
-    const size_t merge = (size_t)NW * a.k * 8;
-    if (lutb < merge) lutb = merge;
-    const size_t tail = (size_t)NW * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 8 + 64 + (size_t)2 * M * DSUB * 4 + 16;
-    const size_t smem = lutb + tail;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(scanm_kernel<M, KPL, NBUF, IMI, DSUB, NWX>), smem);
-    hipLaunchKernelGGL((scanm_kernel<M, KPL, NBUF, IMI, DSUB, NWX>), dim3((unsigned)(8 * a.xcd_chunk)), dim3(64 * NW), smem, s, a, (int)lutb);
+static bool launch_scanm_i(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    constexpr int NW = NWX ? NWX : ScanMShape<M>::NW;
+    if (L.nw != NW || L.nbuf != NBUF) return false;          // (the plan's LDS bytes are those of its own wave and buffer counts)
+    ensure_dynamic_lds(reinterpret_cast<const void*>(scanm_kernel<M, KPL, NBUF, IMI, DSUB, NWX>), L.lds_bytes);
+    hipLaunchKernelGGL((scanm_kernel<M, KPL, NBUF, IMI, DSUB, NWX>), dim3((unsigned)(8 * a.xcd_chunk)), dim3(64 * NW), L.lds_bytes, s, a, L.lut_region);
+    return true;
 }
 // table mode 0 (DSUB = d / M components per sub-quantizer)
 template <int M, int DSUB>
-static void launch_scanm0_k(const ScanArgs& a, hipStream_t s) {
-    if (a.k <= 64) launch_scanm_i<M, 1, 2, false, DSUB>(a, s);
-    else if (a.k <= 256) launch_scanm_i<M, 4, 2, false, DSUB>(a, s);
-    else launch_scanm_i<M, 16, 2, false, DSUB>(a, s);
+static bool launch_scanm0_k(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    switch (L.kpl) {
+    case 1: return launch_scanm_i<M, 1, 2, false, DSUB>(a, L, s);
+    case 4: return launch_scanm_i<M, 4, 2, false, DSUB>(a, L, s);
+    case 16: return launch_scanm_i<M, 16, 2, false, DSUB>(a, L, s);
+    }
+    return false;
 }
 template <int M, int NBUF>
-static void launch_scanm_k(const ScanArgs& a, hipStream_t s) {
-#define VLQ_SM(K)                                                       \
-    do {                                                                \
-        if (a.imi_nbits > 0) launch_scanm_i<M, K, NBUF, true>(a, s);    \
-        else launch_scanm_i<M, K, NBUF, false>(a, s);                   \
-    } while (0)
-    // 8-byte codes, k <= 64, 3000 queries and more: two waves per workgroup.  The kernel is bound by the instructions it issues
-    // (profiles/r05_code_sizes.txt: 4100 VALU + 2400 SALU per wave at four waves, 3/4 of them per-probe work every wave
-    // repeats -- metadata, addresses, table build, threshold -- for 1.3 trips of 8 gathers); two waves halve that share
-    if (M == 8 && a.k <= 64 && a.nq * a.nsplit >= 3000) {
-        if (a.imi_nbits > 0) launch_scanm_i<M, 1, NBUF, true, 0, M == 8 ? 2 : 0>(a, s);
-        else launch_scanm_i<M, 1, NBUF, false, 0, M == 8 ? 2 : 0>(a, s);
-    } else if (a.k <= 64) VLQ_SM(1);
-    else if (a.k <= 128) VLQ_SM(2);
-    else if (a.k <= 256) VLQ_SM(4);
-    else VLQ_SM(16);
+static bool launch_scanm_k(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+#define VLQ_SM(K) return L.imi ? launch_scanm_i<M, K, NBUF, true>(a, L, s) : launch_scanm_i<M, K, NBUF, false>(a, L, s)
+    // (two waves per workgroup: 8-byte codes only -- plan_scan has the rule)
+    if (M == 8 && L.kpl == 1 && L.nw == 2)
+        return L.imi ? launch_scanm_i<M, 1, NBUF, true, 0, M == 8 ? 2 : 0>(a, L, s) : launch_scanm_i<M, 1, NBUF, false, 0, M == 8 ? 2 : 0>(a, L, s);
+    switch (L.kpl) {
+    case 1: VLQ_SM(1);
+    case 2: VLQ_SM(2);
+    case 4: VLQ_SM(4);
+    case 16: VLQ_SM(16);
+    }
 #undef VLQ_SM
+    return false;
 }
 
-// table mode 0 on the engineered kernel: 8-, 16- and 32-byte codes, flat coarse quantizer, d <= 128 (a thread holds d codebook floats)
-bool scanm0_supports(const ScanArgs& a) {
-    if (!(a.table_mode == 0 && a.ksub == 256 && a.imi_nbits == 0 && a.coarse && a.pq_cent && a.queries && a.nprobe <= 1024)) return false;
-    if (a.M == 16) return a.dsub == 4 || a.dsub == 6 || a.dsub == 8;
-    if (a.M == 8) return a.dsub == 8 || a.dsub == 12 || a.dsub == 16;
-    if (a.M == 32) return a.dsub == 2 || a.dsub == 4;         // (round 5: d = 64 / 128; 64-byte codes would put the second table
-    return false;                                             //  buffer past the 16-bit offset of the gather instructions)
-}
-
-bool scanm_supports(const ScanArgs& a) {
-    return (a.M == 4 || a.M == 8 || a.M == 12 || (a.M >= 20 && a.M <= 32 && a.M % 4 == 0) || (a.M >= 40 && a.M <= 64 && a.M % 8 == 0)) &&
-           a.ksub == 256 && a.table_mode == 1 && (a.qtab || a.pq_cent_t) && a.term2 &&
-           a.nprobe <= 1024 &&
-           (a.imi_nbits == 0 || a.M % 2 == 0);
-}
-
-void launch_scanm(const ScanArgs& a_in, hipStream_t s) {
-    if (a_in.nq <= 0) return;
-    ScanArgs a = a_in;
-    if (a.nsplit < 1) a.nsplit = 1;
-    a.xcd_chunk = (int)((a.nq * a.nsplit + 7) / 8);
+// the instantiation plan_scan chose (scan_plan.h), for the code size and -- table mode 0 -- the sub-vector length of the index
+bool launch_scanm(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
     if (a.table_mode == 0) {
-        if (a.M == 16) {
-            if (a.dsub == 8) launch_scanm0_k<16, 8>(a, s);
-            else if (a.dsub == 6) launch_scanm0_k<16, 6>(a, s);
-            else launch_scanm0_k<16, 4>(a, s);
-        } else if (a.M == 32) {
-            if (a.dsub == 4) launch_scanm0_k<32, 4>(a, s);
-            else launch_scanm0_k<32, 2>(a, s);
-        } else {
-            if (a.dsub == 16) launch_scanm0_k<8, 16>(a, s);
-            else if (a.dsub == 12) launch_scanm0_k<8, 12>(a, s);
-            else launch_scanm0_k<8, 8>(a, s);
+        // 8-, 16- and 32-byte codes, flat coarse quantizer, d <= 128 (a thread holds d codebook floats)
+        switch (a.M * 100 + a.dsub) {
+        case 1608: return launch_scanm0_k<16, 8>(a, L, s);
+        case 1606: return launch_scanm0_k<16, 6>(a, L, s);
+        case 1604: return launch_scanm0_k<16, 4>(a, L, s);
+        case 3204: return launch_scanm0_k<32, 4>(a, L, s);
+        case 3202: return launch_scanm0_k<32, 2>(a, L, s);
+        case 816: return launch_scanm0_k<8, 16>(a, L, s);
+        case 812: return launch_scanm0_k<8, 12>(a, L, s);
+        case 808: return launch_scanm0_k<8, 8>(a, L, s);
         }
-        return;
+        return false;
     }
     // (round 5: 4-, 12-, 20-, 24-, 28-, 40-, 48- and 56-byte codes -- the other multiples of 4 bytes that the reference
     // instantiates, gpu/impl/IVFPQ.cu:149-172 -- are the same template: ceil(M / 8) half blocks, the last one of 4 where M is
     // not a multiple of 8, one table buffer, 4 waves up to 32 bytes, 8 above)
     switch (a.M) {
-    case 8: launch_scanm_k<8, 2>(a, s); break;
-    case 4: launch_scanm_k<4, 1>(a, s); break;
-    case 12: launch_scanm_k<12, 1>(a, s); break;
-    case 20: launch_scanm_k<20, 1>(a, s); break;
-    case 24: launch_scanm_k<24, 1>(a, s); break;
-    case 28: launch_scanm_k<28, 1>(a, s); break;
-    case 32: launch_scanm_k<32, 1>(a, s); break;      // one 32 KB buffer, 4 waves (ScanMShape)
-    case 40: launch_scanm_k<40, 1>(a, s); break;
-    case 48: launch_scanm_k<48, 1>(a, s); break;
-    case 56: launch_scanm_k<56, 1>(a, s); break;
-    default: launch_scanm_k<64, 1>(a, s); break;
+    case 8: return launch_scanm_k<8, 2>(a, L, s);
+    case 4: return launch_scanm_k<4, 1>(a, L, s);
+    case 12: return launch_scanm_k<12, 1>(a, L, s);
+    case 20: return launch_scanm_k<20, 1>(a, L, s);
+    case 24: return launch_scanm_k<24, 1>(a, L, s);
+    case 28: return launch_scanm_k<28, 1>(a, L, s);
+    case 32: return launch_scanm_k<32, 1>(a, L, s);      // one 32 KB buffer, 4 waves (ScanMShape)
+    case 40: return launch_scanm_k<40, 1>(a, L, s);
+    case 48: return launch_scanm_k<48, 1>(a, L, s);
+    case 56: return launch_scanm_k<56, 1>(a, L, s);
+    case 64: return launch_scanm_k<64, 1>(a, L, s);
     }
+    return false;
 }
 
 void preload_scanm_kernels() {

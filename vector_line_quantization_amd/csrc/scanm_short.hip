@@ -150,12 +150,6 @@ __global__ __launch_bounds__(256) void scanm_short_kernel(ScanArgs a, int queue_
     if (badkey) *a.bad_key = 1;
 }
 
-bool scanm_short_supports(const ScanArgs& a) {
-    const bool size_ok = a.M == 4 || a.M == 8 || a.M == 12 || (a.M >= 20 && a.M <= 32 && a.M % 4 == 0) || (a.M >= 40 && a.M <= 64 && a.M % 8 == 0);
-    return size_ok && a.ksub == 256 && a.table_mode == 1 && a.term2 && a.qtab && a.nprobe <= 1024 && a.k >= 1 && a.k <= 1024 && a.nsplit == 1 &&
-           a.tail_r == 0;
-}
-
 template <int M, int KPL>
 static void launch_scanm_short_t(const ScanArgs& a, int queue_off, size_t smem, hipStream_t s) {
     ensure_dynamic_lds(reinterpret_cast<const void*>(scanm_short_kernel<M, KPL>), smem);
@@ -163,34 +157,31 @@ static void launch_scanm_short_t(const ScanArgs& a, int queue_off, size_t smem, 
 }
 
 template <int M>
-static void launch_scanm_short_m(const ScanArgs& a, hipStream_t s) {
-    size_t region = (size_t)M * 256 * 4;                    // the merge area aliases the table
-    const size_t merge = (size_t)4 * a.k * 8;
-    if (region < merge) region = merge;
-    const size_t smem = region + (size_t)4 * 64 * 8 + (size_t)a.nprobe * 24 + 8 + 8 + (size_t)a.nprobe * 2 + 64;
-    if (a.k <= 64) launch_scanm_short_t<M, 1>(a, (int)region, smem, s);
-    else if (a.k <= 256) launch_scanm_short_t<M, 4>(a, (int)region, smem, s);
-    else launch_scanm_short_t<M, 16>(a, (int)region, smem, s);
+static bool launch_scanm_short_m(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    switch (L.kpl) {
+    case 1: launch_scanm_short_t<M, 1>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 4: launch_scanm_short_t<M, 4>(a, L.lut_region, L.lds_bytes, s); return true;
+    case 16: launch_scanm_short_t<M, 16>(a, L.lut_region, L.lds_bytes, s); return true;
+    }
+    return false;
 }
 
-void launch_scanm_short(const ScanArgs& a_in, hipStream_t s) {
-    if (a_in.nq <= 0) return;
-    ScanArgs a = a_in;
-    a.xcd_chunk = (int)((a.nq + 7) / 8);
-    a.short_keep_order = 0;          // (multi-index cells by halves; the coarse-order walk was a retired A/B)
+bool launch_scanm_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
+    if (a.nq <= 0) return true;
     switch (a.M) {
-    case 4: launch_scanm_short_m<4>(a, s); break;
-    case 8: launch_scanm_short_m<8>(a, s); break;
-    case 12: launch_scanm_short_m<12>(a, s); break;
-    case 20: launch_scanm_short_m<20>(a, s); break;
-    case 24: launch_scanm_short_m<24>(a, s); break;
-    case 28: launch_scanm_short_m<28>(a, s); break;
-    case 32: launch_scanm_short_m<32>(a, s); break;
-    case 40: launch_scanm_short_m<40>(a, s); break;
-    case 48: launch_scanm_short_m<48>(a, s); break;
-    case 56: launch_scanm_short_m<56>(a, s); break;
-    default: launch_scanm_short_m<64>(a, s); break;
+    case 4: return launch_scanm_short_m<4>(a, L, s);
+    case 8: return launch_scanm_short_m<8>(a, L, s);
+    case 12: return launch_scanm_short_m<12>(a, L, s);
+    case 20: return launch_scanm_short_m<20>(a, L, s);
+    case 24: return launch_scanm_short_m<24>(a, L, s);
+    case 28: return launch_scanm_short_m<28>(a, L, s);
+    case 32: return launch_scanm_short_m<32>(a, L, s);
+    case 40: return launch_scanm_short_m<40>(a, L, s);
+    case 48: return launch_scanm_short_m<48>(a, L, s);
+    case 56: return launch_scanm_short_m<56>(a, L, s);
+    case 64: return launch_scanm_short_m<64>(a, L, s);
     }
+    return false;
 }
 
 }  // namespace vlq
