@@ -120,7 +120,7 @@ struct IndexIVFPQ : IndexIVF {
   void add_core_o(idx_t n, const float* x, const long* xids, float* residuals_2,
                   const long* precomputed_idx = nullptr) {
     FAISS_THROW_IF_NOT(is_trained);
-    FAISS_THROW_IF_NOT_MSG(!residuals_2 && !precomputed_idx, "IVFPQR / precomputed_idx are outside the built path");
+    FAISS_THROW_IF_NOT_MSG(!precomputed_idx, "precomputed_idx is outside the built path");
     if (n == 0) return;
     sync_(false);
     std::vector<int64_t> idx(n);
@@ -128,9 +128,19 @@ struct IndexIVFPQ : IndexIVF {
     VLQ_CHECK(vlq_ivfpq_encode(h_, n, x, idx.data(), xcodes.data()));
     for (idx_t i = 0; i < n; i++) {
       const int64_t key = idx[i];
-      if (key < 0) continue;
+      if (key < 0) {
+        if (residuals_2) memset(residuals_2 + i * d, 0, sizeof(float) * d);
+        continue;
+      }
       ids[key].push_back(xids ? xids[i] : ntotal + i);
       codes[key].insert(codes[key].end(), &xcodes[i * code_size], &xcodes[(i + 1) * code_size]);
+      if (residuals_2) {   // IndexIVFPQ.cpp:250-256: what was encoded minus its reconstruction
+        float* res2 = residuals_2 + i * d;
+        std::vector<float> enc(x + i * d, x + (i + 1) * d);
+        if (by_residual) quantizer->compute_residual(x + i * d, enc.data(), key);
+        pq.decode(&xcodes[i * code_size], res2);
+        for (int j = 0; j < d; j++) res2[j] = enc[j] - res2[j];
+      }
       if (maintain_direct_map) direct_map.push_back(key << 32 | (long)(ids[key].size() - 1));
     }
     ntotal += n;
@@ -314,7 +324,7 @@ struct IndexIVFPQ : IndexIVF {
   /// handle of the device copy (GpuIndexIVFPQ::copyFrom reads the host fields instead)
   vlq_ivfpq_t device_handle() const { sync_(true); return h_; }
 
- private:
+ protected:
   void check_search_() const {
     FAISS_THROW_IF_NOT(is_trained);
     FAISS_THROW_IF_NOT_MSG(polysemous_ht == 0 && scan_table_threshold == 0,
@@ -360,6 +370,127 @@ struct IndexIVFPQ : IndexIVF {
   }
   mutable vlq_ivfpq_t h_ = nullptr;
   mutable bool hdirty_ = true, ldirty_ = true;
+};
+
+/// faiss::IndexIVFPQR (IndexIVFPQ.h:200-225, IndexIVFPQ.cpp:1289-1479): IndexIVFPQ with a re-ranking stage on the device.
+/// The host `refine_codes` are indexed by id as in the reference (valid for ids 0 .. ntotal-1, IndexIVFPQ.cpp:1429-1431) and
+/// mirrored to the device by list slot, beside the PQ codes.
+struct IndexIVFPQR : IndexIVFPQ {
+  ProductQuantizer refine_pq;            ///< 3rd level quantizer
+  std::vector<uint8_t> refine_codes;     ///< corresponding codes, by id
+  float k_factor;                        ///< factor between k requested in search and the k requested from the IVFPQ
+
+  IndexIVFPQR(Index* quantizer, size_t d, size_t nlist, size_t M, size_t nbits_per_idx, size_t M_refine, size_t nbits_per_idx_refine)
+      : IndexIVFPQ(quantizer, d, nlist, M, nbits_per_idx), refine_pq(d, M_refine, nbits_per_idx_refine), k_factor(4) {
+    FAISS_THROW_IF_NOT(nbits_per_idx_refine <= 8);
+    by_residual = true;
+  }
+  IndexIVFPQR() : k_factor(1) { by_residual = true; }
+  ~IndexIVFPQR() override { if (hr_) vlq_ivfpq_destroy(hr_); }
+
+  void reset() override {
+    IndexIVFPQ::reset();
+    refine_codes.clear();
+    rdirty_ = true;
+  }
+
+  /// IndexIVFPQ.cpp:1317-1334: the refine quantizer is trained on the second-level residuals of the training set
+  void train_residual(idx_t n, const float* x) override {
+    std::vector<float> residual_2((size_t)n * d);
+    train_residual_o(n, x, residual_2.data());
+    const size_t filled = std::min((size_t)n, (size_t)pq.cp.max_points_per_centroid * pq.ksub);   // rows train_residual_o wrote
+    refine_pq.cp.max_points_per_centroid = 1000;
+    refine_pq.cp.verbose = verbose;
+    refine_pq.train((int)filled, residual_2.data());
+    rpq_dirty_ = true;
+  }
+
+  void add_with_ids(idx_t n, const float* x, const long* xids) override { add_core(n, x, xids, nullptr); }
+
+  /// IndexIVFPQ.cpp:1341-1357; refine_pq.compute_codes runs on the device (the encoder without its residual step)
+  void add_core(idx_t n, const float* x, const long* xids, const long* precomputed_idx = nullptr) {
+    std::vector<float> residual_2((size_t)n * d);
+    const idx_t n0 = ntotal;
+    add_core_o(n, x, xids, residual_2.data(), precomputed_idx);
+    refine_codes.resize((size_t)ntotal * refine_pq.code_size);
+    if (n > 0) {
+      // ProductQuantizer::compute_codes takes BLAS tables there (ProductQuantizer.cpp:385-407): not bit-reproducible
+      FAISS_THROW_IF_NOT_MSG(refine_pq.dsub < 16, "add with d / M_refine >= 16 is outside the built path (load refine_codes instead)");
+      const IndexFlat* flat = dynamic_cast<const IndexFlat*>(quantizer);
+      FAISS_THROW_IF_NOT_MSG(flat, "IVFPQR needs a flat coarse quantizer");
+      if (!hr_) VLQ_CHECK(vlq_ivfpq_create(&hr_, device, d, (int)nlist, (int)refine_pq.M, (int)refine_pq.nbits));
+      VLQ_CHECK(vlq_ivfpq_set_coarse_centroids(hr_, flat->xb.data()));
+      VLQ_CHECK(vlq_ivfpq_set_pq_centroids(hr_, refine_pq.centroids.data()));
+      VLQ_CHECK(vlq_ivfpq_set_search_options(hr_, 0, 0, 0));
+      std::vector<int64_t> zero(n, 0);
+      VLQ_CHECK(vlq_ivfpq_encode_preassigned(hr_, n, residual_2.data(), zero.data(), &refine_codes[(size_t)n0 * refine_pq.code_size]));
+    }
+    rdirty_ = true;
+  }
+
+  /// IndexIVFPQ.cpp:1360-1447 on the device: coarse stage, first stage with store_pairs at long(k * k_factor), refine stage
+  void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override {
+    check_search_();
+    sync_refine_();
+    VLQ_CHECK(vlq_ivfpq_search_refined(h_, n, x, (int)nprobe, (int)k, k_factor, distances, (int64_t*)labels));
+    collect_stats_(n);
+    indexIVFPQ_stats.nrefine += (size_t)n * (size_t)(long)((float)k * k_factor);
+  }
+
+  /// IndexIVFPQ.cpp:1449-1464 (row i - i0 of recons: the reference indexes it with i)
+  void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override {
+    std::vector<float> r3(d);
+    IndexIVFPQ::reconstruct_n(i0, ni, recons);
+    for (idx_t i = i0; i < i0 + ni; i++) {
+      float* r = recons + (size_t)(i - i0) * d;
+      refine_pq.decode(&refine_codes[(size_t)i * refine_pq.code_size], r3.data());
+      for (int j = 0; j < d; j++) r[j] += r3[j];
+    }
+  }
+
+  void merge_from_residuals(IndexIVF& other_in) override {   // IndexIVFPQ.cpp:1466-1473
+    IndexIVFPQR& other = dynamic_cast<IndexIVFPQR&>(other_in);
+    IndexIVFPQ::merge_from_residuals(other);
+    refine_codes.insert(refine_codes.end(), other.refine_codes.begin(), other.refine_codes.end());
+    other.refine_codes.clear();
+    rdirty_ = other.rdirty_ = true;
+  }
+
+  long remove_ids(const IDSelector&) override {   // IndexIVFPQ.cpp:1475-1479
+    FAISS_THROW_MSG("not implemented");
+    return 0;
+  }
+
+  /// after writing refine_pq.centroids / refine_codes / the lists directly (read_index, a copy from another index)
+  void refine_changed() { rpq_dirty_ = rdirty_ = true; }
+
+ private:
+  void sync_refine_() const {
+    bool relist = ldirty_ || rdirty_;
+    sync_(true);
+    if (rpq_dirty_) {
+      VLQ_CHECK(vlq_ivfpq_set_refine_pq(h_, (int)refine_pq.M, (int)refine_pq.nbits, refine_pq.centroids.data()));
+      rpq_dirty_ = false;
+      relist = true;
+    }
+    if (relist) {   // by id on the host, by list slot on the device
+      const size_t cs = refine_pq.code_size;
+      size_t stored = 0;
+      for (size_t i = 0; i < nlist; i++) stored += ids[i].size();
+      std::vector<uint8_t> fr(stored * cs);
+      size_t s = 0;
+      for (size_t i = 0; i < nlist; i++)
+        for (size_t j = 0; j < ids[i].size(); j++, s++) {
+          const long id = ids[i][j];
+          FAISS_THROW_IF_NOT_MSG(id >= 0 && (size_t)(id + 1) * cs <= refine_codes.size(), "IVFPQR: ids must be 0 .. ntotal-1 (IndexIVFPQ.cpp:1429-1431)");
+          memcpy(&fr[s * cs], &refine_codes[(size_t)id * cs], cs);
+        }
+      VLQ_CHECK(vlq_ivfpq_set_refine_codes(h_, fr.data()));
+      rdirty_ = false;
+    }
+  }
+  mutable vlq_ivfpq_t hr_ = nullptr;       // encoder of the refine codes
+  mutable bool rpq_dirty_ = true, rdirty_ = true;
 };
 
 }  // namespace faiss

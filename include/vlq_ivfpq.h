@@ -184,6 +184,47 @@ int vlq_ivfpq_search_preassigned(vlq_ivfpq_t h, int64_t n, const float* x, const
 int vlq_ivfpq_coarse_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe,
                             float* coarse_dis, int64_t* keys);
 
+/* ---- IVFPQR: IndexIVFPQ with a re-ranking stage (IndexIVFPQ.h:200-225, IndexIVFPQ.cpp:1289-1479; the index
+ * tests/demo_sift1M.cpp:98 builds, "IVF4096,PQ8+16").  The first stage returns k_coarse = long(k * k_factor) candidates as
+ * (list, offset) pairs; every candidate is re-scored with a second product quantizer trained on the first stage's
+ * residuals, bit for bit in the reference's operation order (fvec_L2sqr, utils.cpp:481-506).  Flat coarse quantizer and
+ * by_residual only (the reference's constructor forces by_residual, :1297; a multi-index quantizer has no reconstruct):
+ * VLQ_ERR_UNSUPPORTED otherwise.  Entry points above behave exactly as before while no refine quantizer is set.
+ *
+ * IndexIVFPQR::refine_pq (IndexIVFPQ.h:201): centroids [M_refine][2^nbits_refine][d / M_refine], nbits_refine <= 8.  [h|d]
+ * Refine codes loaded earlier are dropped. */
+int vlq_ivfpq_set_refine_pq(vlq_ivfpq_t h, int M_refine, int nbits_refine, const float* centroids);
+/* IndexIVFPQR::refine_codes (IndexIVFPQ.h:202) -- stored BY LIST SLOT here, not by id: refine_codes[ntotal][M_refine] u8 in
+ * the list-contiguous order of the `codes` given to vlq_ivfpq_set_lists (row i belongs to the vector of codes row i), so
+ * the search needs no id indirection (IndexIVFPQ.cpp:1429-1431 is only right for ids 0 .. ntotal-1) and any ids work.
+ * vlq_ivfpq_set_lists after this call drops the refine codes.  [h|d] */
+int vlq_ivfpq_set_refine_codes(vlq_ivfpq_t h, const uint8_t* refine_codes);
+/* refine codes of one list, in list order (beside vlq_ivfpq_get_list); out is a host buffer [list length][M_refine] */
+int vlq_ivfpq_get_list_refine_codes(vlq_ivfpq_t h, int list_id, uint8_t* out);
+/* vlq_ivfpq_add with a refine quantizer set is IndexIVFPQR::add_core (IndexIVFPQ.cpp:1341-1357): the second-level
+ * residual (:250-256) and its refine code (first minimum wins) are computed on the device and appended with the vector.
+ * d / M_refine >= 16 goes through BLAS tables in the reference (ProductQuantizer.cpp:385-407) and cannot be
+ * bit-reproduced: add returns VLQ_ERR_UNSUPPORTED there (loading codes and searching still work).
+ * vlq_ivfpq_reserve_memory / vlq_ivfpq_reclaim_memory keep the refine array in step with the lists.
+ *
+ * The refine seam: the loop of IndexIVFPQR::search, IndexIVFPQ.cpp:1392-1444, alone.  shortlist[n][k_coarse] holds pair
+ * labels list << 32 | offset (-1 = skip) as vlq_ivfpq_search_preassigned(store_pairs) returns them; D / I [n][k] are the k
+ * smallest (refined distance, shortlist position), ascending, padded with FLT_MAX / -1; labels are the stored ids.
+ * k, k_coarse <= VLQ_MAX_K.  All buffers [h|d].  A pair outside the lists is reported like a bad key of
+ * vlq_ivfpq_search_preassigned: VLQ_ERR_INVALID from this call with a host D or I, from the next vlq_ivfpq_stats() otherwise. */
+int vlq_ivfpq_refine(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* shortlist, int k_coarse, int k,
+                     float* D, int64_t* I);
+/* IndexIVFPQR::search (IndexIVFPQ.cpp:1360-1447) whole: quantizer->search, search_knn_with_key with store_pairs at
+ * k_coarse = long(k * k_factor) (:1375), the refine loop; the shortlist never leaves the device.
+ * k_coarse outside 1 .. VLQ_MAX_K: VLQ_ERR_INVALID.  Without a refine quantizer, or with stored vectors that have no
+ * refine code, the three search calls return VLQ_ERR_STATE.  x, D, I [h|d]. */
+int vlq_ivfpq_search_refined(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe, int k, float k_factor,
+                             float* D, int64_t* I);
+/* the same from given probes (keys / coarse_dis [n][nprobe] as in vlq_ivfpq_search_preassigned, nprobe <= VLQ_MAX_NPROBE) */
+int vlq_ivfpq_search_refined_preassigned(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* keys,
+                                         const float* coarse_dis, int nprobe, int k, float k_factor, float* D,
+                                         int64_t* I);
+
 /* Merge of per-shard results for indexes whose inverted lists are split over GPUs / ranks
  * (GpuIndexIVFPQ::merge, gpu/GpuIndexIVFPQ.cu:1467-1591, used by gpu/test/deep1b16_query.cpp
  * after the gather; IndexShards::search merge, MetaIndexes.cpp:486-557).  D_parts / I_parts

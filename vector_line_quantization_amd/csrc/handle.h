@@ -139,6 +139,12 @@ struct vlq_ivfpq_s {
     std::vector<int64_t> h_list_off, h_list_len;   // host copies, refreshed on demand (lists_sync_host)
     bool h_lists_stale = false;
     AppendWs ws_append;
+    // IVFPQR (IndexIVFPQ.h:200-225): the refine quantizer and its codes, stored by list slot beside `codes` (same starts,
+    // lengths and capacities: refine code of slot s at rcodes[s * Mr]).  have_rcodes: every stored vector has one.
+    int Mr = 0, nbits_r = 0, ksub_r = 0, dsub_r = 0;
+    DevBuf rpq, rcodes;
+    bool have_rpq = false, have_rcodes = false;
+    DevBuf ws_sl, ws_Dsl, ws_r2, ws_rcodes;   // shortlist labels / distances of search_refined, r2 and refine codes of an add batch
 
     // workspace
     DevBuf ws_Dp, ws_Ip;          // partial top-k rows of the split scan (small batches)

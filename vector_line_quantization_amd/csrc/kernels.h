@@ -289,4 +289,28 @@ void launch_residual_encode(const float* x, int64_t n, int d, const float* coars
                             const int64_t* assign, int by_residual, const float* cent, int M,
                             int ksub, int dsub, uint8_t* codes, hipStream_t s, int imi_nbits = 0);
 
+// IVFPQR (refine.hip): the re-ranking loop of IndexIVFPQR::search (IndexIVFPQ.cpp:1392-1444).  shortlist [nq][k_coarse] holds
+// list << 32 | offset labels (-1 = skip); a pair outside the lists sets *bad = 4 and is skipped.  D / I [nq][k].
+struct RefineArgs {
+    const float* x;              // [nq][d]
+    const int64_t* shortlist;    // [nq][k_coarse]
+    const float* coarse;         // [nlist][d]
+    const float* pq;             // [M][ksub][dsub]
+    const float* rpq;            // [Mr][ksub_r][dsub_r]
+    const uint8_t* codes;        // [cap][M]
+    const uint8_t* rcodes;       // [cap][Mr]
+    const int64_t* ids;          // [cap]
+    const int64_t* list_off;     // [nlist+1]
+    const int64_t* list_len;     // [nlist]
+    float* D;
+    int64_t* I;
+    int* bad;
+    int64_t nq;
+    int k_coarse, k, d, nlist, M, ksub, dsub, Mr, ksub_r, dsub_r;
+};
+void launch_refine(const RefineArgs& a, hipStream_t s);
+// out[i] = (x[i] - coarse[assign[i]]) - pq.decode(codes[i])  (IndexIVFPQ.cpp:250-256; assign < 0: zeros)
+void launch_residual2(const float* x, int64_t n, int d, const float* coarse, const int64_t* assign, const float* pq,
+                      const uint8_t* codes, int M, int ksub, int dsub, float* out, hipStream_t s);
+
 }  // namespace vlq

@@ -1,4 +1,4 @@
-// Device-resident inverted lists: one flat array per field (codes, optional lambda bytes,
+// Device-resident inverted lists: one flat array per field (codes, optional lambda bytes / refine codes,
 // ids), list i at [off[i], off[i] + len[i]) with capacity off[i+1] - off[i].  Lists loaded
 // with set_lists are packed (capacity == length); lists grown by add() get 25 % slack when
 // the layout has to be rebuilt, so appending is amortised O(batch) and never leaves the
@@ -14,7 +14,8 @@ struct ListStore {
     int64_t nlist = 0;
     int code_size = 0;
     DevBuf* codes = nullptr;        // [cap_total][code_size]
-    DevBuf* lambdas = nullptr;      // [cap_total] or nullptr (plain IVFPQ)
+    DevBuf* lambdas = nullptr;      // [cap_total][side_size] or nullptr: a second per-vector field (VLQ: the lambda byte;
+    int side_size = 1;              // IVFPQR: the refine code of side_size = M_refine bytes, IndexIVFPQ.h:200-202)
     DevBuf* ids = nullptr;          // [cap_total] int64
     DevBuf* off = nullptr;          // [nlist+1] int64 list starts (off[nlist] = cap_total)
     DevBuf* len = nullptr;          // [nlist] int64

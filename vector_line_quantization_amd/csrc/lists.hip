@@ -29,7 +29,7 @@ constexpr int kShortList = 32;
 __global__ __launch_bounds__(256) void relayout_kernel(const uint8_t* __restrict__ oc, const uint8_t* __restrict__ ol,
                                                        const int64_t* __restrict__ oi, const int64_t* __restrict__ old_off,
                                                        const int64_t* __restrict__ len, const int64_t* __restrict__ new_off,
-                                                       int64_t nlist, int code_size, uint8_t* __restrict__ nc,
+                                                       int64_t nlist, int code_size, int side_size, uint8_t* __restrict__ nc,
                                                        uint8_t* __restrict__ nl, int64_t* __restrict__ ni) {
     __shared__ int longs[256];
     __shared__ int nlong;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void relayout_kernel(const uint8_t* __restrict
                 for (int64_t j = 0; j < n * code_size; j++) nc[dn * code_size + j] = oc[so * code_size + j];
             }
             for (int64_t j = 0; j < n; j++) ni[dn + j] = oi[so + j];
-            if (ol) for (int64_t j = 0; j < n; j++) nl[dn + j] = ol[so + j];
+            if (ol) for (int64_t j = 0; j < n * side_size; j++) nl[dn * side_size + j] = ol[so * side_size + j];
         }
     }
     __syncthreads();
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void relayout_kernel(const uint8_t* __restrict
             for (int64_t j = threadIdx.x; j < bytes; j += 256) dst[j] = src[j];
         }
         for (int64_t j = threadIdx.x; j < n; j += 256) ni[dn + j] = oi[so + j];
-        if (ol) for (int64_t j = threadIdx.x; j < n; j += 256) nl[dn + j] = ol[so + j];
+        if (ol) for (int64_t j = threadIdx.x; j < n * side_size; j += 256) nl[dn * side_size + j] = ol[so * side_size + j];
     }
 }
 
@@ -106,7 +106,7 @@ __global__ void place_kernel(const unsigned long long* __restrict__ sorted, int6
                              const int64_t* __restrict__ cstart, const int64_t* __restrict__ off,
                              const int64_t* __restrict__ len, const uint8_t* __restrict__ new_codes,
                              const uint8_t* __restrict__ new_lambdas, const int64_t* __restrict__ xids,
-                             int64_t id_base, int code_size, uint8_t* __restrict__ codes,
+                             int64_t id_base, int code_size, int side_size, uint8_t* __restrict__ codes,
                              uint8_t* __restrict__ lambdas, int64_t* __restrict__ ids) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -122,7 +122,7 @@ __global__ void place_kernel(const unsigned long long* __restrict__ sorted, int6
     } else {
         for (int b = 0; b < code_size; b++) d[b] = src[b];
     }
-    if (lambdas) lambdas[dst] = new_lambdas[i];
+    if (lambdas) for (int b = 0; b < side_size; b++) lambdas[dst * side_size + b] = new_lambdas[i * side_size + b];
     ids[dst] = xids ? xids[i] : id_base + i;
 }
 
@@ -147,7 +147,7 @@ static int relayout_dev(ListStore& ls, DevBuf& noff, int64_t cap, hipStream_t s)
     DevBuf nc, nl, ni;
     int rc = nc.reserve((size_t)cap * ls.code_size + 16);
     if (rc == VLQ_OK) rc = ni.reserve((size_t)cap * 8 + 16);
-    if (rc == VLQ_OK && ls.lambdas) rc = nl.reserve((size_t)cap + 16);
+    if (rc == VLQ_OK && ls.lambdas) rc = nl.reserve((size_t)cap * ls.side_size + 16);
     if (rc != VLQ_OK) { nc.release(); nl.release(); ni.release(); noff.release(); return rc; }
     hipError_t e = hipSuccess;
     if (ls.codes->p) {
@@ -155,7 +155,7 @@ static int relayout_dev(ListStore& ls, DevBuf& noff, int64_t cap, hipStream_t s)
         hipLaunchKernelGGL(relayout_kernel, dim3(g), dim3(256), 0, s, ls.codes->as<uint8_t>(),
                            ls.lambdas ? ls.lambdas->as<uint8_t>() : nullptr, ls.ids->as<int64_t>(),
                            ls.off->as<int64_t>(), ls.len->as<int64_t>(), noff.as<int64_t>(), nlist,
-                           ls.code_size, nc.as<uint8_t>(), ls.lambdas ? nl.as<uint8_t>() : nullptr,
+                           ls.code_size, ls.side_size, nc.as<uint8_t>(), ls.lambdas ? nl.as<uint8_t>() : nullptr,
                            ni.as<int64_t>());
         e = hipGetLastError();
     }
@@ -210,7 +210,7 @@ int lists_reclaim(ListStore& ls, uint64_t* bytes, hipStream_t s) {
     std::vector<int64_t> new_off((size_t)ls.nlist + 1, 0);
     for (int64_t i = 0; i < ls.nlist; i++) new_off[(size_t)i + 1] = new_off[(size_t)i] + h_len[(size_t)i];
     const int64_t new_cap = new_off[(size_t)ls.nlist];
-    if (bytes) *bytes = (uint64_t)(old_cap - new_cap) * (uint64_t)(ls.code_size + 8 + (ls.lambdas ? 1 : 0));
+    if (bytes) *bytes = (uint64_t)(old_cap - new_cap) * (uint64_t)(ls.code_size + 8 + (ls.lambdas ? ls.side_size : 0));
     if (new_cap == old_cap) return VLQ_OK;
     return lists_relayout(ls, new_off, s);
 }
@@ -290,7 +290,7 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
     // 3. place the batch, then publish the new lengths
     hipLaunchKernelGGL(place_kernel, dim3(grid), dim3(256), 0, s, ws.keys_out.as<unsigned long long>(), n,
                        ws.cstart.as<int64_t>(), ls.off->as<int64_t>(), ls.len->as<int64_t>(), new_codes,
-                       new_lambdas, xids, id_base, ls.code_size, ls.codes->as<uint8_t>(),
+                       new_lambdas, xids, id_base, ls.code_size, ls.side_size, ls.codes->as<uint8_t>(),
                        ls.lambdas ? ls.lambdas->as<uint8_t>() : nullptr, ls.ids->as<int64_t>());
     hipLaunchKernelGGL(add_counts_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), nlist, ls.len->as<int64_t>());
     HIP_TRY(hipGetLastError());

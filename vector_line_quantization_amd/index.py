@@ -205,6 +205,60 @@ class GpuIVFPQ:
         check(lib().vlq_ivfpq_coarse_search(self._h, C.c_int64(n), px, C.c_int(nprobe), pc, pk))
         return cdis, keys
 
+    # --- IVFPQR: the re-ranking stage (IndexIVFPQ.h:200-225) -----------------
+    def set_refine_pq(self, M_refine, nbits_refine, centroids):
+        """IndexIVFPQR::refine_pq: centroids [M_refine][2^nbits_refine][d / M_refine]"""
+        p, _k = _ptr(centroids, np.float32)
+        check(lib().vlq_ivfpq_set_refine_pq(self._h, C.c_int(M_refine), C.c_int(nbits_refine), p))
+        self.M_refine, self.nbits_refine = M_refine, nbits_refine
+
+    def set_refine_codes(self, refine_codes):
+        """refine codes [ntotal][M_refine] in the list-contiguous order of set_lists' codes (by list slot, not by id)"""
+        p, _k = _ptr(refine_codes, np.uint8)
+        check(lib().vlq_ivfpq_set_refine_codes(self._h, p))
+
+    def get_list_refine_codes(self, i):
+        out = np.empty((self.list_length(i), getattr(self, "M_refine", 0)), np.uint8)
+        check(lib().vlq_ivfpq_get_list_refine_codes(self._h, C.c_int(i), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def refine(self, x, shortlist, k, D=None, I=None):
+        """the loop of IndexIVFPQR::search alone: shortlist [n][k_coarse] of list << 32 | offset labels (-1 = skip)"""
+        n, k_coarse = x.shape[0], shortlist.shape[1]
+        px, _a = _ptr(x, np.float32)
+        ps, _b = _ptr(shortlist, np.int64)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _c = _out_ptr(D, np.float32)
+        pI, _d = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfpq_refine(self._h, C.c_int64(n), px, ps, C.c_int(k_coarse), C.c_int(k), pD, pI))
+        return D, I
+
+    def search_refined(self, x, nprobe, k, k_factor, D=None, I=None):
+        """IndexIVFPQR::search: first stage at k_coarse = long(k * k_factor), then the refine stage"""
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _b = _out_ptr(D, np.float32)
+        pI, _c = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfpq_search_refined(self._h, C.c_int64(n), px, C.c_int(nprobe), C.c_int(k), C.c_float(k_factor), pD, pI))
+        return D, I
+
+    def search_refined_preassigned(self, x, keys, coarse_dis, k, k_factor, D=None, I=None):
+        n = x.shape[0]
+        nprobe = keys.shape[1]
+        px, _a = _ptr(x, np.float32)
+        pk, _b = _ptr(keys, np.int64)
+        pc, _c = _ptr(coarse_dis, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _d = _out_ptr(D, np.float32)
+        pI, _e = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfpq_search_refined_preassigned(self._h, C.c_int64(n), px, pk, pc, C.c_int(nprobe), C.c_int(k),
+                                                         C.c_float(k_factor), pD, pI))
+        return D, I
+
     # --- introspection ----------------------------------------------------
     def query_tables(self, x, inner_product=True):
         n = x.shape[0]
