@@ -32,7 +32,7 @@ struct IndexIVFPQ : IndexIVF {
   size_t code_size;
   ProductQuantizer pq;
   bool do_polysemous_training;
-  void* polysemous_training;       // unused: polysemous_ht != 0 is outside the path
+  void* polysemous_training;       // unused: training the permutation is outside the path (polysemous_ht is honoured)
   size_t scan_table_threshold;
   size_t max_codes;
   int polysemous_ht;
@@ -327,14 +327,18 @@ struct IndexIVFPQ : IndexIVF {
  protected:
   void check_search_() const {
     FAISS_THROW_IF_NOT(is_trained);
-    FAISS_THROW_IF_NOT_MSG(polysemous_ht == 0 && scan_table_threshold == 0,
-                           "polysemous / on-the-fly scan modes are outside the built path");
+    FAISS_THROW_IF_NOT_MSG(scan_table_threshold == 0, "the on-the-fly scan mode is outside the built path");
+    FAISS_THROW_IF_NOT_MSG(polysemous_ht >= 0, "polysemous_ht < 0");
   }
   void collect_stats_(size_t n) const {
-    uint64_t nq = 0, ncode = 0;
+    uint64_t nq = 0, ncode = 0, npass = 0;
     VLQ_CHECK(vlq_ivfpq_stats(h_, &nq, &ncode, 1));   // also raises on an invalid key (IndexIVFPQ.cpp:1008-1011)
     indexIVFPQ_stats.nq += n;
     indexIVFPQ_stats.ncode += ncode;
+    if (polysemous_ht > 0) {                          // IndexIVFPQ.cpp:1048
+      VLQ_CHECK(vlq_ivfpq_polysemous_stats(h_, &npass, 1));
+      indexIVFPQ_stats.n_hamming_pass += npass;
+    }
   }
   void sync_(bool with_lists) const {
     const IndexFlat* flat = dynamic_cast<const IndexFlat*>(quantizer);
@@ -354,6 +358,9 @@ struct IndexIVFPQ : IndexIVF {
     }
     VLQ_CHECK(vlq_ivfpq_set_search_options(h_, by_residual, by_residual ? (use_precomputed_table ? 1 : 0) : 0,
                                            (int64_t)max_codes));
+    // polysemous_ht > 0 (IndexIVFPQ.cpp:1023-1025): the filtered scan.  By residual over a flat quantizer the code of the
+    // query is the first argmin of the (query, list) table, not the reference's unwritten one (include/vlq_ivfpq.h)
+    VLQ_CHECK(vlq_ivfpq_set_polysemous_ht(h_, polysemous_ht));
     if (with_lists && ldirty_) {
       std::vector<int64_t> off(nlist + 1, 0);
       for (size_t i = 0; i < nlist; i++) off[i + 1] = off[i] + (int64_t)ids[i].size();

@@ -116,7 +116,7 @@ class GpuIndexIVFPQ : public GpuIndex {
   void copyFrom(const faiss::IndexIVFPQ* index) {
     FAISS_THROW_IF_NOT_MSG(index->pq.byte_per_idx == 1, "GPU: only pq.byte_per_idx == 1 is supported");
     FAISS_THROW_IF_NOT_MSG(index->by_residual, "GPU: only by_residual = true is supported");
-    FAISS_THROW_IF_NOT_MSG(index->polysemous_ht == 0, "GPU: polysemous codes not supported");
+    FAISS_THROW_IF_NOT_MSG(index->polysemous_ht >= 0, "GPU: polysemous_ht < 0");
     const IndexFlat* flat = dynamic_cast<const IndexFlat*>(index->quantizer);
     FAISS_THROW_IF_NOT_MSG(flat && flat->metric_type == METRIC_L2,
                            "Only IndexFlatL2 is supported as the coarse quantizer (gpu/GpuIndexIVF.cu:131-133)");
@@ -135,6 +135,9 @@ class GpuIndexIVFPQ : public GpuIndex {
     VLQ_CHECK(vlq_ivfpq_set_pq_centroids(h_, pqCentroids_.data()));
     usePrecomputed_ = ivfpqConfig_.usePrecomputedTables || index->use_precomputed_table == 1;
     VLQ_CHECK(vlq_ivfpq_set_search_options(h_, 1, usePrecomputed_ ? 1 : 0, (int64_t)index->max_codes));
+    // the reference refuses such an index (gpu/GpuIndexIVFPQ.cu:175); here the threshold is copied and the scan filters
+    // (include/vlq_ivfpq.h: which code of the query the stored codes are compared with)
+    VLQ_CHECK(vlq_ivfpq_set_polysemous_ht(h_, index->polysemous_ht));
     std::vector<int64_t> off(nlist_ + 1, 0);
     for (int i = 0; i < nlist_; i++) off[i + 1] = off[i] + (int64_t)index->ids[i].size();
     std::vector<uint8_t> fc((size_t)off[nlist_] * subQuantizers_);

@@ -225,6 +225,37 @@ int vlq_ivfpq_search_refined_preassigned(vlq_ivfpq_t h, int64_t n, const float* 
                                          const float* coarse_dis, int nprobe, int k, float k_factor, float* D,
                                          int64_t* I);
 
+/* ---- Polysemous Hamming filtering: IndexIVFPQ::polysemous_ht (IndexIVFPQ.h:41), scan_list_polysemous_hc
+ * (IndexIVFPQ.cpp:887-947, called at :1023-1025).  ht = 0: off (the default; every call behaves exactly as before).  ht < 0:
+ * VLQ_ERR_INVALID.  With ht > 0 a stored code is looked up and offered to the result only if hd < ht (:901), hd = the
+ * population count of q_code XOR code over the whole code (HammingComputer{4,8,16,20,32,64}, M8 and M4 of hamming.h all give
+ * this number); codes that pass get the arithmetic of scan_list_with_table (:781-802), and admission, store_pairs, the
+ * max_codes cut (:1033, counted in list sizes, not in passed codes) and the ncode of vlq_ivfpq_stats are unchanged.
+ *
+ * q_code[m] is the FIRST argmin over j of the table tab[m][j] the scan itself reads:
+ *   not by_residual                    the query's distance table, once per query = pq.compute_code(qi) (:544-545,
+ *                                      ProductQuantizer.cpp:311-336)
+ *   by_residual, multi-index (type 2)  per (query, list) = what fvec_madd_and_argmin leaves while the list's table is
+ *                                      built (:676-683)
+ *   by_residual, flat (type 0 and 1)   per (query, list), the same rule.  THIS IS NOT WHAT THE REFERENCE DOES: there q_code is
+ *                                      sized in the constructor (:523-525) and never written (precompute_list_tables_L2,
+ *                                      :635-644, does not touch it), so the reference filters on the Hamming weight of the
+ *                                      stored code.  That defect is not reproduced; where the table holds distances (type 0)
+ *                                      the code is compute_code of the residual.
+ * Served with ht > 0: vlq_ivfpq_search, vlq_ivfpq_search_preassigned (store_pairs too), for one byte per sub-quantizer index,
+ * M % 4 == 0, M <= 64, every table mode, flat and multi-index quantizers, k <= VLQ_MAX_K, nprobe <= VLQ_MAX_NPROBE, max_codes.
+ * VLQ_ERR_UNSUPPORTED with ht > 0: any other M, float16 tables, more than VLQ_MAX_NPROBE probes, vlq_ivfpq_refine and the
+ * vlq_ivfpq_search_refined calls.  vlq_ivfpq_coarse_search does not look at the setting; vlq_ivfpq_set_scan_schedule is
+ * ignored while ht > 0 (one kernel serves the mode, csrc/scan_poly.hip). */
+int vlq_ivfpq_set_polysemous_ht(vlq_ivfpq_t h, int ht);
+/* Introspection beside vlq_ivfpq_query_tables: out[n][nprobe][M] (host buffer) = the q_code the scan would use for every
+ * (query, probe) of keys[n][nprobe]; not by_residual the rows of a query are equal; the row of a key outside 0 .. nlist-1
+ * is zero.  x, keys [h|d].  nprobe <= VLQ_MAX_NPROBE.  Independent of the threshold set. */
+int vlq_ivfpq_query_codes(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, uint8_t* out);
+/* indexIVFPQ_stats.n_hamming_pass (IndexIVFPQ.h:169-195, IndexIVFPQ.cpp:902, :1048): codes that passed the filter since the
+ * last reset.  Synchronises the stream, like vlq_ivfpq_stats. */
+int vlq_ivfpq_polysemous_stats(vlq_ivfpq_t h, uint64_t* n_hamming_pass, int reset);
+
 /* Merge of per-shard results for indexes whose inverted lists are split over GPUs / ranks
  * (GpuIndexIVFPQ::merge, gpu/GpuIndexIVFPQ.cu:1467-1591, used by gpu/test/deep1b16_query.cpp
  * after the gather; IndexShards::search merge, MetaIndexes.cpp:486-557).  D_parts / I_parts

@@ -18,7 +18,7 @@
 //
 // The host-side ids / codes vectors stay the authoritative copy (write_index, copy_subset_to, IndexIVFPQR's
 // refinement read them); they are mirrored to HBM, list-contiguously, before the first search after a change.
-// What the device path does not cover (inner-product metric, polysemous filtering, on-the-fly scan threshold,
+// What the device path does not cover (inner-product metric, polysemous filtering by residual over a flat quantizer, on-the-fly scan threshold,
 // BLAS-encoded sub-vectors of >= 16 dimensions, nbits > 8) is handed to the reference's own definition (dlsym RTLD_NEXT).
 //
 // Two conveniences for running the drivers where /home/data does not exist: fopen() and open() of a path
@@ -135,6 +135,17 @@ bool device_shape(const faiss::IndexIVFPQ* ix) {
     return flat_l2(ix) || imi2(ix);
 }
 
+// polysemous_ht > 0 on the device: the modes where the library's code of the query IS the reference's -- not by_residual
+// (pq.compute_code, IndexIVFPQ.cpp:544-545) and table type 2 (fvec_madd_and_argmin, :676-683) -- for M % 4 == 0, M <= 64 and at most
+// VLQ_MAX_NPROBE probes.  By residual with table type 0 or 1 the reference never writes q_code (precompute_list_tables_L2,
+// IndexIVFPQ.cpp:635-644) and filters on the Hamming weight of the stored code; the library defines the code there
+// (include/vlq_ivfpq.h), so those calls keep the reference's own definition and a caller of the reference's classes sees no change.
+bool poly_ok(const faiss::IndexIVFPQ* ix) {
+    if (ix->polysemous_ht == 0) return true;
+    if (ix->polysemous_ht < 0 || ix->pq.M % 4 != 0 || ix->pq.M > 64 || ix->nprobe > VLQ_MAX_NPROBE) return false;
+    return !ix->by_residual || (ix->use_precomputed_table == 2 && imi2(ix) != nullptr);
+}
+
 // device handle of `ix` with its trained state (centroids, codebook, search options) current
 State& sync(const faiss::IndexIVFPQ* ix, bool with_lists) {
     State& st = states[ix];
@@ -171,6 +182,7 @@ State& sync(const faiss::IndexIVFPQ* ix, bool with_lists) {
     check(vlq_ivfpq_set_search_options(st.h, ix->by_residual ? 1 : 0,
                                        ix->by_residual ? (ix->use_precomputed_table ? 1 : 0) : 0, (int64_t)ix->max_codes),
           "vlq_ivfpq_set_search_options");
+    check(vlq_ivfpq_set_polysemous_ht(st.h, poly_ok(ix) ? ix->polysemous_ht : 0), "vlq_ivfpq_set_polysemous_ht");
     if (with_lists) {
         // the lists change through add_core_o (here), but also reset / remove_ids / merge_from / read_index
         // in the reference's own code: a cheap signature decides
@@ -211,7 +223,7 @@ namespace faiss {
 void IndexIVFPQ::search_knn_with_key(size_t nx, const float* qx, const long* keys, const float* coarse_dis,
                                      float_maxheap_array_t* res, bool store_pairs) const {
     KnnTimer knn_timer;
-    const bool on_device = device_shape(this) && polysemous_ht == 0 && scan_table_threshold == 0 &&
+    const bool on_device = device_shape(this) && poly_ok(this) && scan_table_threshold == 0 &&
                            res->k >= 1 && res->k <= VLQ_MAX_K && (nprobe <= VLQ_MAX_NPROBE || (max_codes == 0 && nprobe <= 64 * VLQ_MAX_NPROBE)) &&
                            !(imi2(this) && by_residual && use_precomputed_table == 0);
     if (!on_device) {
@@ -234,6 +246,11 @@ void IndexIVFPQ::search_knn_with_key(size_t nx, const float* qx, const long* key
     uint64_t nq = 0, ncode = 0;
     check(vlq_ivfpq_stats(st.h, &nq, &ncode, 1), "vlq_ivfpq_stats");     // also raises on a key >= nlist (IndexIVFPQ.cpp:1008-1011)
     indexIVFPQ_stats.nq += nx;
+    if (polysemous_ht > 0) {             // IndexIVFPQ.cpp:1048
+        uint64_t npass = 0;
+        check(vlq_ivfpq_polysemous_stats(st.h, &npass, 1), "vlq_ivfpq_polysemous_stats");
+        indexIVFPQ_stats.n_hamming_pass += npass;
+    }
     indexIVFPQ_stats.ncode += ncode;
     cnt.searches++;
     cnt.queries += nx;
@@ -303,7 +320,7 @@ void IndexIVFPQ::search(idx_t n, const float* x, idx_t k, float* distances, idx_
     // (the quantizer's own search() must be the one replaced: a subclass may override it)
     const bool plain_quantizer = quantizer && ((mi && typeid(*quantizer) == typeid(MultiIndexQuantizer)) ||
                                                (fl && (typeid(*quantizer) == typeid(IndexFlatL2) || typeid(*quantizer) == typeid(IndexFlat))));
-    const bool on_device = !whole_off && plain_quantizer && polysemous_ht == 0 && scan_table_threshold == 0 && k >= 1 && k <= VLQ_MAX_K &&
+    const bool on_device = !whole_off && plain_quantizer && poly_ok(this) && scan_table_threshold == 0 && k >= 1 && k <= VLQ_MAX_K &&
                            nprobe >= 1 && (mi ? (nprobe <= VLQ_MAX_IMI_NPROBE && (nprobe <= VLQ_MAX_NPROBE || max_codes == 0)) : nprobe <= VLQ_MAX_NPROBE) &&
                            nprobe <= nlist && !(mi && by_residual && use_precomputed_table == 0);
     if (!on_device) {
@@ -321,6 +338,11 @@ void IndexIVFPQ::search(idx_t n, const float* x, idx_t k, float* distances, idx_
     uint64_t nq = 0, ncode = 0;
     check(vlq_ivfpq_stats(st.h, &nq, &ncode, 1), "vlq_ivfpq_stats");
     indexIVFPQ_stats.nq += n;
+    if (polysemous_ht > 0) {             // IndexIVFPQ.cpp:1048
+        uint64_t npass = 0;
+        check(vlq_ivfpq_polysemous_stats(st.h, &npass, 1), "vlq_ivfpq_polysemous_stats");
+        indexIVFPQ_stats.n_hamming_pass += npass;
+    }
     indexIVFPQ_stats.ncode += ncode;
     cnt.searches++;
     cnt.whole++;

@@ -437,9 +437,81 @@ int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* 
     return VLQ_OK;
 }
 
+// polysemous_ht > 0 (IndexIVFPQ.cpp:1023-1025): the filtered scan (scan_poly.hip), chosen before the scan plan is consulted.
+// qcodes != nullptr: no scan, the q_code of every (query, probe) into qcodes[n][nprobe][M] (vlq_ivfpq_query_codes).
+int scan_poly_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev, const float* cdis_dev, int nprobe, int k,
+                  float* D_dev, int64_t* I_dev, int store_pairs, uint8_t* qcodes) {
+    if (!vlq::poly_shape_ok(h->M, h->ksub))
+        return fail(VLQ_ERR_UNSUPPORTED, "polysemous filtering is built for M %% 4 == 0, M <= 64 (M = %d)", h->M);
+    if (h->fp16_tables) return fail(VLQ_ERR_UNSUPPORTED, "polysemous filtering with float16 look-up tables is not built");
+    if (nprobe > vlq::kPolyMaxProbes)
+        return fail(VLQ_ERR_UNSUPPORTED, "polysemous filtering with nprobe=%d > %d is not built", nprobe, vlq::kPolyMaxProbes);
+    TRY(ensure_term2(h));
+    const size_t E = (size_t)h->M * h->ksub;
+    const int table_mode = !h->by_residual ? 2 : (h->use_precomputed_table == 1 ? 1 : 0);
+    if (h->imi_nbits > 0 && table_mode == 0)
+        return fail(VLQ_ERR_UNSUPPORTED, "multi-index coarse quantizer without the precomputed table (type 2) is not built");
+    const int64_t page = 32768;
+    for (int64_t i0 = 0; i0 < n; i0 += page) {
+        const int64_t ni = std::min(page, n - i0);
+        const float* xi = x_dev + i0 * h->d;
+        if (table_mode != 0) {
+            TRY(h->ws_qtab.reserve((size_t)ni * E * sizeof(float)));
+            StageTimer tm(h, 1);
+            // init_query_L2 (IndexIVFPQ.cpp:557-563): ip table (mode 1) or distance table
+            vlq::launch_pq_tables(xi, ni, h->d, h->pq.as<float>(), h->M, h->ksub, h->dsub, nullptr, table_mode == 1 ? 0 : 1,
+                                  h->ws_qtab.as<float>(), h->stream);
+            tm.stop();
+        }
+        vlq::ScanArgs a;
+        a.codes = h->codes.as<uint8_t>();
+        a.ids = h->ids.as<int64_t>();
+        a.list_off = h->list_off.as<int64_t>();
+        a.list_len = h->list_len.as<int64_t>();
+        a.term2 = table_mode == 1 ? h->term2.as<float>() : nullptr;
+        a.qtab = table_mode != 0 ? h->ws_qtab.as<float>() : nullptr;
+        a.queries = xi;
+        a.coarse = h->coarse.as<float>();
+        a.pq_cent = h->pq.as<float>();
+        a.keys = keys_dev + i0 * nprobe;
+        a.coarse_dis = cdis_dev + i0 * nprobe;
+        a.D = D_dev ? D_dev + i0 * k : nullptr;
+        a.I = I_dev ? I_dev + i0 * k : nullptr;
+        a.ncode = h->stats.as<unsigned long long>();
+        a.bad_key = reinterpret_cast<int*>(h->stats.as<unsigned long long>() + 1);
+        a.nq = ni;
+        a.nprobe = nprobe; a.k = k; a.M = h->M; a.ksub = h->ksub; a.dsub = h->dsub; a.d = h->d;
+        a.nlist = h->nlist;
+        a.table_mode = table_mode;
+        a.imi_nbits = h->imi_nbits;
+        a.max_codes = h->max_codes;
+        a.store_pairs = store_pairs;
+        vlq::PolyArgs pa;
+        pa.ht = h->polysemous_ht;
+        pa.n_pass = h->poly_stats.as<unsigned long long>();
+        pa.qcodes = qcodes ? qcodes + (size_t)i0 * nprobe * h->M : nullptr;
+        if (qcodes) {       // introspection: not a scan, no stage time booked
+            if (!vlq::launch_scan_poly(a, pa, h->stream)) return fail(VLQ_ERR_HIP, "internal: the polysemous scan is not built for this shape");
+            continue;
+        }
+        StageTimer tm(h, 2);
+        if (!vlq::launch_scan_poly(a, pa, h->stream)) return fail(VLQ_ERR_HIP, "internal: the polysemous scan is not built for this shape");
+        tm.stop();
+        if (!qcodes) snprintf(h->last_scan, sizeof(h->last_scan), "scan_poly_kernel<%d>", h->M / 4);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!qcodes) {
+        h->stat_nq += (uint64_t)n;
+        h->last_walk_first = -1; h->last_walk_limit = 0; h->last_walk_samples = 0; h->last_walk_counts = false;
+        h->order_hist_ready = false;
+    }
+    return VLQ_OK;
+}
+
 int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev,
              const float* cdis_dev, int nprobe, int k, float* D_dev, int64_t* I_dev,
              int store_pairs) {
+    if (h->polysemous_ht > 0) return scan_poly_dev(h, n, x_dev, keys_dev, cdis_dev, nprobe, k, D_dev, I_dev, store_pairs, nullptr);
     TRY(ensure_term2(h));
     const vlq::Env& env = vlq::env();
     const size_t E = (size_t)h->M * h->ksub;
@@ -805,12 +877,14 @@ int vlq_ivfpq_create(vlq_ivfpq_t* out, int device, int d, int nlist, int M, int 
     if (const char* e = getenv("VLQ_COARSE_FILTER")) h->coarse_filter = atoi(e);   // 1: filtered coarse stage (A/B; slower)
     h->h_lists_stale = true;    // host copies of the list starts / lengths are filled on first use
     int rc = h->stats.reserve(512);    // [0] ncode, [1] flag word; [2..7] phase clocks of instrumented builds (-DVLQ_PHASE_TIMING), [8..47] (-DVLQ_SCAN16_PHASES)
+    if (rc == VLQ_OK) rc = h->poly_stats.reserve(8);
     if (rc == VLQ_OK) rc = h->list_off.reserve(((size_t)nlist + 1) * 8);
     if (rc == VLQ_OK) rc = h->list_len.reserve((size_t)nlist * 8);
     if (rc == VLQ_OK) rc = h->codes.reserve(16);
     if (rc == VLQ_OK) rc = h->ids.reserve(16);
     if (rc != VLQ_OK) { vlq_ivfpq_destroy(h); return rc; }
     (void)hipMemsetAsync(h->stats.p, 0, 512, h->stream);
+    (void)hipMemsetAsync(h->poly_stats.p, 0, 8, h->stream);
     (void)hipMemsetAsync(h->list_off.p, 0, ((size_t)nlist + 1) * 8, h->stream);
     (void)hipMemsetAsync(h->list_len.p, 0, (size_t)nlist * 8, h->stream);
     (void)hipStreamSynchronize(h->stream);
@@ -836,7 +910,7 @@ void vlq_ivfpq_destroy(vlq_ivfpq_t h) {
                       &h->screen.half, &h->screen.mu, &h->screen.norm_c, &h->imi_screen[0].half, &h->imi_screen[0].mu,
                       &h->imi_screen[0].norm_c, &h->imi_screen[1].half, &h->imi_screen[1].mu, &h->imi_screen[1].norm_c,
                       &h->ws_qn_c, &h->ws_xh, &h->ws_xflags, &h->ws_screen_cnt,
-                      &h->rpq, &h->rcodes, &h->ws_sl, &h->ws_Dsl, &h->ws_r2, &h->ws_rcodes};
+                      &h->rpq, &h->rcodes, &h->ws_sl, &h->ws_Dsl, &h->ws_r2, &h->ws_rcodes, &h->poly_stats, &h->ws_qcodes};
     for (auto b : bufs) b->release();
     if (h->screen_cnt_host) (void)hipHostFree(h->screen_cnt_host);
     for (DevBuf* b : {&h->imi_ws2.xh, &h->imi_ws2.xflags, &h->imi_ws2.qn, &h->imi_ws2.qn_c, &h->imi_ws2.cand, &h->imi_ws2.tmin}) b->release();
@@ -1097,6 +1171,43 @@ int vlq_ivfpq_coarse_screen_state(vlq_ivfpq_t h, int* enabled, uint64_t* rows, u
     return VLQ_OK;
 }
 
+int vlq_ivfpq_set_polysemous_ht(vlq_ivfpq_t h, int ht) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (ht < 0) return fail(VLQ_ERR_INVALID, "polysemous_ht=%d < 0", ht);
+    h->polysemous_ht = ht;
+    return VLQ_OK;
+}
+
+int vlq_ivfpq_query_codes(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, uint8_t* out) {
+    TRY(check_ready(h, false));        // as vlq_ivfpq_query_tables: the codes do not depend on the lists
+    if (n < 0 || nprobe < 1 || (n > 0 && (!x || !keys || !out))) return fail(VLQ_ERR_INVALID, "bad argument");
+    if (n == 0) return VLQ_OK;
+    TRY(set_dev(h));
+    const void *xd, *kd;
+    TRY(stage_in(h, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(h, keys, (size_t)n * nprobe * 8, h->ws_keys_in, &kd));
+    const size_t bytes = (size_t)n * nprobe * h->M;
+    TRY(h->ws_qcodes.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(h->ws_qcodes.p, 0, bytes, h->stream));       // rows of key -1 stay zero
+    TRY(h->ws_cdis.reserve((size_t)n * nprobe * 4));                    // (the probe records carry a coarse distance; q_code does not depend on it)
+    HIP_TRY(hipMemsetAsync(h->ws_cdis.p, 0, (size_t)n * nprobe * 4, h->stream));
+    TRY(scan_poly_dev(h, n, (const float*)xd, (const int64_t*)kd, h->ws_cdis.as<float>(), nprobe, 1, nullptr, nullptr, 0, h->ws_qcodes.as<uint8_t>()));
+    HIP_TRY(hipMemcpyAsync(out, h->ws_qcodes.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return VLQ_OK;
+}
+
+int vlq_ivfpq_polysemous_stats(vlq_ivfpq_t h, uint64_t* n_hamming_pass, int reset) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    TRY(set_dev(h));
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, h->poly_stats.p, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (n_hamming_pass) *n_hamming_pass = v;
+    if (reset) HIP_TRY(hipMemsetAsync(h->poly_stats.p, 0, 8, h->stream));
+    return VLQ_OK;
+}
+
 int vlq_ivfpq_set_scan_schedule(vlq_ivfpq_t h, int mode) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (mode < 0 || mode > 4) return fail(VLQ_ERR_INVALID, "scan schedule %d outside 0..4", mode);
@@ -1204,6 +1315,8 @@ int vlq_ivfpq_coarse_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe
 static int scan_runs_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const int64_t* kd, const float* cd, int nprobe, int k, float* Dd,
                          int64_t* Id, int store_pairs) {
     if (nprobe <= VLQ_MAX_NPROBE) return scan_dev(h, n, xd, kd, cd, nprobe, k, Dd, Id, store_pairs);
+    if (h->polysemous_ht > 0)
+        return fail(VLQ_ERR_UNSUPPORTED, "polysemous filtering with nprobe=%d > %d (runs of probes) is not built", nprobe, VLQ_MAX_NPROBE);
     if (h->max_codes != 0)
         return fail(VLQ_ERR_UNSUPPORTED, "max_codes=%lld with nprobe=%d > %d: the limit would apply to every run of probes, not to the "
                     "whole list (IndexIVFPQ.cpp:1052)", (long long)h->max_codes, nprobe, VLQ_MAX_NPROBE);
@@ -1578,6 +1691,7 @@ static int refine_shape_ok(vlq_ivfpq_t h) {
 static int refine_ready(vlq_ivfpq_t h) {
     TRY(refine_shape_ok(h));
     TRY(check_ready(h, true));
+    if (h->polysemous_ht > 0) return fail(VLQ_ERR_UNSUPPORTED, "IVFPQR with polysemous filtering is not built");
     if (!h->have_rpq) return fail(VLQ_ERR_STATE, "refine quantizer not set (vlq_ivfpq_set_refine_pq)");
     if (h->ntotal > 0 && !h->have_rcodes) return fail(VLQ_ERR_STATE, "the stored vectors have no refine codes (vlq_ivfpq_set_refine_codes)");
     return VLQ_OK;

@@ -166,6 +166,9 @@ struct vlq_ivfpq_s {
     bool fp16_tables = false, term2h_valid = false;
     DevBuf term2h, ws_qtabh;
     DevBuf stats;   // [0] ncode (u64), [1] bad key flag (int)
+    // polysemous filtering (IndexIVFPQ::polysemous_ht, IndexIVFPQ.h:41): 0 = off; codes that passed the filter (u64, device)
+    int polysemous_ht = 0;
+    DevBuf poly_stats, ws_qcodes;
     uint64_t stat_nq = 0;
 
     // profiling

@@ -235,6 +235,35 @@ bool launch_scan16_bigk(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 bool launch_scan16_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
 // the same organisation for the other code sizes (4 ... 64 bytes in the steps scanm.hip serves; per-query table in a.qtab)
 bool launch_scanm_short(const ScanArgs& a, const ScanLaunch& L, hipStream_t s);
+// Polysemous Hamming filtering (IndexIVFPQ::polysemous_ht > 0, IndexIVFPQ.cpp:887-947; scan_poly.hip): a stored code is looked up
+// only if popcount(q_code XOR code) < ht.  One byte per sub-quantizer index, M a multiple of 4 up to 64, every table mode.
+// n_pass: += codes that passed (indexIVFPQ_stats.n_hamming_pass).  qcodes != nullptr: no scan -- the kernel builds every
+// probe's table and leaves its q_code in qcodes[nq][nprobe][M] (rows of keys outside 0 .. nlist-1 are not written).
+struct PolyArgs {
+    int ht = 0;
+    unsigned long long* n_pass = nullptr;
+    uint8_t* qcodes = nullptr;
+};
+constexpr int kPolyMaxProbes = 1024;
+inline bool poly_shape_ok(int M, int ksub) { return M >= 4 && M <= 64 && M % 4 == 0 && ksub <= 256; }
+// the kernel's dynamic LDS, byte offsets: the table (later the merge area of the four waves' rows) at 0, the selections'
+// queues, the passer rings, the probe metadata, the workgroup's pass count, the list's q_code, the residual of table mode 0
+struct PolyLayout { int selq, ring, meta, misc, qcode, sres; size_t bytes; };
+inline PolyLayout poly_layout(int M, int ksub, int nprobe, int k, int d) {
+    PolyLayout l;
+    const size_t table = (size_t)M * ksub * 4, merge = (size_t)4 * k * 8;
+    size_t o = ((table > merge ? table : merge) + 15) & ~(size_t)15;
+    l.selq = (int)o; o += 4 * 64 * 8;
+    l.ring = (int)o; o += 4 * 128 * 4;
+    l.meta = (int)o; o += (probe_meta_bytes(nprobe) + 7) & ~(size_t)7;
+    l.misc = (int)o; o += 8;
+    l.qcode = (int)o; o += 64;
+    l.sres = (int)o; o += (size_t)d * 4;
+    l.bytes = o;
+    return l;
+}
+bool launch_scan_poly(const ScanArgs& a, const PolyArgs& p, hipStream_t s);
+
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this
 inline size_t query_order_bins_padded(int nlist) {

@@ -103,6 +103,20 @@ class GpuIVFPQ:
         """0 automatic, 1 query-major, 2 list-owned (speed only; include/vlq_ivfpq.h)"""
         check(lib().vlq_ivfpq_set_scan_schedule(self._h, C.c_int(int(mode))))
 
+    def set_polysemous_ht(self, ht):
+        """IndexIVFPQ::polysemous_ht: 0 off; > 0 only codes within that Hamming distance of the query's code are looked up
+        (include/vlq_ivfpq.h says which code that is in every mode)"""
+        check(lib().vlq_ivfpq_set_polysemous_ht(self._h, C.c_int(int(ht))))
+        self._polysemous_ht = int(ht)
+
+    @property
+    def polysemous_ht(self):
+        return getattr(self, "_polysemous_ht", 0)
+
+    @polysemous_ht.setter
+    def polysemous_ht(self, ht):
+        self.set_polysemous_ht(ht)
+
     def set_lists(self, codes, ids, list_offsets):
         pc, _a = _ptr(codes, np.uint8)
         pi, _b = _ptr(ids, np.int64)
@@ -267,6 +281,21 @@ class GpuIVFPQ:
         check(lib().vlq_ivfpq_query_tables(self._h, C.c_int64(n), px, C.c_int(int(inner_product)),
                                            out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def query_codes(self, x, keys):
+        """q_code [n][nprobe][M] the polysemous filter compares the stored codes of every (query, probe) with"""
+        n, nprobe = x.shape[0], keys.shape[1]
+        px, _a = _ptr(x, np.float32)
+        pk, _b = _ptr(keys, np.int64)
+        out = np.empty((n, nprobe, self.M), np.uint8)
+        check(lib().vlq_ivfpq_query_codes(self._h, C.c_int64(n), px, pk, C.c_int(nprobe), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def polysemous_stats(self, reset=False):
+        """indexIVFPQ_stats.n_hamming_pass: codes that passed the Hamming filter since the last reset"""
+        n = C.c_uint64()
+        check(lib().vlq_ivfpq_polysemous_stats(self._h, C.byref(n), C.c_int(int(reset))))
+        return n.value
 
     def precomputed_table(self, rows=None):
         out = np.empty((rows or self.nlist, self.M, self.ksub), np.float32)

@@ -100,3 +100,10 @@ def merge_shard_results(D_parts, I_parts, k):
     # padding (-1 / FLT_MAX) of shards with fewer than k hits sorts last by its distance
     order = torch.sort(D, dim=1, stable=True).indices[:, :k]
     return torch.gather(D, 1, order), torch.gather(I, 1, order)
+
+
+def set_polysemous_ht(index, ht):
+    """IndexIVFPQ::polysemous_ht for a sharded search: every rank calls this with the same threshold and sets it on its own
+    handle.  Replica or list range alike, the filter acts per stored code, so shards filter exactly as one index would; each
+    rank searches only its own handle, so no collective is needed."""
+    index.set_polysemous_ht(ht)
