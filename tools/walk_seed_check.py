@@ -20,7 +20,7 @@ for name, kw in (("headline", dict(sigma=0.005, rank=12, spread=0.4)), ("G1", di
         for _ in range(6):
             g.reset_walk_state(); torch.cuda.synchronize()
             t0 = time.perf_counter(); g.search(xq, nprobe, k, D=D, I=I); torch.cuda.synchronize(); tc.append(time.perf_counter() - t0)
-            seeds.append(g.last_scan_info().split("launch_period_ticks=")[1])
+            seeds.append(g.last_scan_info().split("launch_period_ticks=")[1].split()[0])
             for _ in range(3): g.search(xq, nprobe, k, D=D, I=I)
             torch.cuda.synchronize()
             t0 = time.perf_counter(); g.search(xq, nprobe, k, D=D, I=I); torch.cuda.synchronize(); tw.append(time.perf_counter() - t0)

@@ -587,19 +587,26 @@ int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_d
         // the scan order of the queries (and, QueryOrder::walk, the walk statistic and the decision of the walking order from
         // it); booked with the table stage -- the caller holds its StageTimer
         auto order_queries = [&]() -> int {
+            h->last_placement = "none";
             if (plan.order == vlq::QueryOrder::none) return VLQ_OK;
             TRY(h->ws_hist.reserve(2 * vlq::query_order_bins_padded(h->nlist) * sizeof(int)));
             TRY(h->ws_qorder.reserve(((size_t)ni + 40) * sizeof(int)));
             const int* rank = plan.order_by_rank ? h->list_rank.as<int>() : nullptr;
+            // the probes vote for the key on the pages that take the walk order (scan_plan.h: order_vote; placement_key.h)
+            const uint8_t* lpart = plan.order_vote ? h->list_part.as<uint8_t>() : nullptr;
+            TRY(h->ws_qkey.reserve((size_t)ni * sizeof(uint32_t)));
+            h->last_placement = lpart ? "vote" : rank ? "nearest-rank" : "nearest-id";
             if (plan.order == vlq::QueryOrder::plain) {
-                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank);
+                vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank,
+                                        nullptr, nullptr, vlq::WalkSeed(), true, false, lpart, h->ws_qkey.as<uint32_t>());
             } else {
                 vlq::WalkSeed wseed;
                 wseed.list_off = h->list_off.as<int64_t>(); wseed.list_len = h->list_len.as<int64_t>(); wseed.nlist = h->nlist;
                 wseed.slots = plan.walk_seed_slots;
                 int* counts = walk_auto ? h->walk_counts.as<int>() : nullptr;
                 vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank,
-                                        counts, a.walk_state, wseed, walk_stat_now, h->order_hist_ready && plan.order_hist_ready);
+                                        counts, a.walk_state, wseed, walk_stat_now, h->order_hist_ready && plan.order_hist_ready,
+                                        lpart, h->ws_qkey.as<uint32_t>());
                 if (walk_auto) {
                     const int samples = vlq::walk_stat_samples(ni, nprobe);
                     a.walk_limit = (int)((int64_t)samples * (plan.walk_limit_full ? 1000 : env.walk_share) / 1000);
@@ -904,7 +911,7 @@ void vlq_ivfpq_destroy(vlq_ivfpq_t h) {
                       &h->ws_own_count, &h->ws_part_mask, &h->ws_part_keys, &h->ws_own_recs, &h->ws_own_seg, &h->ws_own_items, &h->coarse_s, &h->cnorm_s, &h->ws_cand, &h->ws_cnt, &h->ws_Dp, &h->ws_Ip, &h->ws_append.cnt, &h->ws_append.cstart, &h->ws_append.keys_in,
                       &h->ws_append.keys_out, &h->ws_append.sort_tmp, &h->ws_x, &h->ws_qn, &h->ws_dist, &h->ws_keys, &h->ws_cdis,
                       &h->ws_qtab, &h->ws_D, &h->ws_I, &h->ws_misc, &h->ws_keys_in, &h->ws_cdis_in,
-                      &h->ws_codes, &h->ws_assign, &h->ws_hist, &h->ws_qorder, &h->ws_tmin, &h->walk_state, &h->stats, &h->imi_cent, &h->ws_Dr, &h->ws_Ir, &h->ws_keys_run, &h->ws_cdis_run, &h->walk_counts,
+                      &h->ws_codes, &h->ws_assign, &h->ws_hist, &h->ws_qorder, &h->ws_qkey, &h->ws_tmin, &h->walk_state, &h->stats, &h->imi_cent, &h->ws_Dr, &h->ws_Ir, &h->ws_keys_run, &h->ws_cdis_run, &h->walk_counts,
                       &h->imi_norm, &h->imi_virtual, &h->ws_imi,
                       // the float16 screen of the coarse stage: built for every index at set_coarse_centroids
                       &h->screen.half, &h->screen.mu, &h->screen.norm_c, &h->imi_screen[0].half, &h->imi_screen[0].mu,
@@ -1413,6 +1420,10 @@ int vlq_ivfpq_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe, int k
         HIP_TRY(hipMemsetAsync(h->ws_hist.p, 0, 2 * stride * sizeof(int), h->stream));
         h->order_hist.hist = h->ws_hist.as<int>();
         h->order_hist.list_rank = h->have_rank ? h->list_rank.as<int>() : nullptr;
+        // (have_rank, no multi-index: what plan_scan's order_vote asks of a walk-order page, the only one that takes these counts)
+        h->order_hist.list_part = h->have_rank ? h->list_part.as<uint8_t>() : nullptr;
+        TRY(h->ws_qkey.reserve((size_t)n * sizeof(uint32_t)));
+        h->order_hist.qkey = h->ws_qkey.as<uint32_t>();
         h->order_hist.nlist = h->nlist;
         vlq::query_order_bins(h->nlist, &h->order_hist.shift, &h->order_hist.nbins);
     }
@@ -1523,9 +1534,9 @@ int vlq_ivfpq_last_scan_info(vlq_ivfpq_t h, char* buf, int cap) {
         HIP_TRY(hipMemcpy(ws, h->walk_state.p, sizeof(ws), hipMemcpyDeviceToHost));
         period = ws[0]; launch_period = ws[1];
     }
-    snprintf(buf, (size_t)cap, "kernel=%s order=%s first=%d shared=%d/%d limit=%d period_ticks=%d launch_period_ticks=%d",
+    snprintf(buf, (size_t)cap, "kernel=%s order=%s first=%d shared=%d/%d limit=%d period_ticks=%d launch_period_ticks=%d placement=%s",
              h->last_scan[0] ? h->last_scan : "none", order, h->last_walk_first, shared, h->last_walk_samples, h->last_walk_limit, period,
-             launch_period);
+             launch_period, h->last_placement);
     return VLQ_OK;
 }
 

@@ -38,6 +38,7 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "placement_key.h"
 #include "sse_order.cuh"
 #include "wave_topk.cuh"
 
@@ -886,11 +887,15 @@ __global__ __launch_bounds__(256) void coarse_screen_exact_kernel(const uint32_t
             const bool miss = key == kMaxKey;
             cdis[q * nprobe + e] = miss ? FLT_MAX_F : ordered_to_f32((uint32_t)(key >> 32));
             keys[q * nprobe + e] = miss ? -1 : (int64_t)(uint32_t)key;
-            if (e == 0 && oh.hist) {            // the scan order's histogram over the rows' nearest centroids (qorder_hist_kernel's bins)
-                const int64_t k0 = miss ? -1 : (int64_t)(uint32_t)key;
-                const bool ok = k0 >= 0 && k0 < oh.nlist;
-                atomicAdd(&oh.hist[ok ? ((oh.list_rank ? oh.list_rank[k0] : (int)k0) >> oh.shift) : oh.nbins - 1], 1);
-            }
+        }
+    }
+    if (oh.hist) {          // the scan order's histogram (qorder_hist_kernel's keys and bins): lane e holds the row's e-th nearest probe
+        const u64 key = sel.best[0];
+        const uint32_t r = placement_rank_wave(key == kMaxKey ? -1 : (int64_t)(uint32_t)key, lane < nprobe, oh.nlist, oh.list_rank,
+                                               oh.list_part);
+        if (lane == 0) {
+            if (oh.qkey) oh.qkey[q] = r;
+            atomicAdd(&oh.hist[placement_bin(r, oh.shift, oh.nbins)], 1);
         }
     }
 }

@@ -151,10 +151,11 @@ struct vlq_ivfpq_s {
     DevBuf ws_Dr, ws_Ir;          // rows of the runs of a search with more than VLQ_MAX_NPROBE probes
     DevBuf ws_keys_run, ws_cdis_run;   // ... and one run's keys / coarse distances (ws_keys / ws_cdis hold the whole probe list)
     DevBuf ws_x, ws_qn, ws_dist, ws_keys, ws_cdis, ws_qtab, ws_D, ws_I, ws_misc, ws_keys_in,
-        ws_cdis_in, ws_codes, ws_assign, ws_hist, ws_qorder, ws_tmin, walk_state;
+        ws_cdis_in, ws_codes, ws_assign, ws_hist, ws_qorder, ws_qkey, ws_tmin, walk_state;
     int64_t walk_key = -1;       // (nprobe, k, batch class) the walk times in walk_state were measured for
     vlq::OrderHist order_hist;   // the scan order's histogram taken along by the coarse stage (vlq_ivfpq_search only)
     bool order_hist_ready = false;
+    const char* last_placement = "none";   // the key the last scan's queries were sorted onto the XCDs by (vlq_ivfpq_last_scan_info)
     int64_t walk_stat_calls = 0; // searches of that key so far (the neighbour-sharing statistic is re-sampled on some of them only)
     // what the last search_dev scan launch was (vlq_ivfpq_last_scan_info): kernel shape, the walking-order rule and the
     // device-side statistic it was decided from (32 counts behind the scan order)

@@ -90,7 +90,12 @@ bool coarse_screen_matrix_free_ok(int nlist, int nprobe);    // the screen witho
 // The scan order's histogram (launch_query_order: counting sort of the queries by their nearest centroid) taken along by the
 // coarse stage's last kernel, which holds every row's nearest centroid anyway: hist[bin(keys[q][0])] += 1 (hist zeroed by the
 // caller; the bins are launch_query_order's: query_order_bins).  One launch and its gap less per search.
-struct OrderHist { int* hist = nullptr; const int* list_rank = nullptr; int shift = 0, nbins = 0, nlist = 0; };
+// The key of a row is placement_rank (placement_key.h) of its probes; with list_part they vote, and the kernel leaves every
+// row's key in qkey[q] for the placement kernel, which then reads no probe at all.
+struct OrderHist {
+    int* hist = nullptr; const int* list_rank = nullptr; int shift = 0, nbins = 0, nlist = 0;
+    const uint8_t* list_part = nullptr; uint32_t* qkey = nullptr;
+};
 void query_order_bins(int nlist, int* shift, int* nbins);
 // qn / cn: exact squared norms (reference order) of queries / centroids; qn_c / cn_c: of the centred ones; cmax = max |c - mu|
 void launch_coarse_screened(const float* q, const void* q_half, const unsigned char* q_flags, const float* c, const void* c_half,
@@ -278,10 +283,13 @@ inline size_t query_order_bins_padded(int nlist) {
 struct WalkSeed { const int64_t* list_off = nullptr; const int64_t* list_len = nullptr; int nlist = 0; int slots = 0; };
 int launch_walk_stat(const int64_t* keys, const int* qorder, int64_t nq, int nprobe, int* part, int* walk_state, hipStream_t s,
                      WalkSeed seed = WalkSeed());
-// list_rank (optional): bins are the spatial ranks of the lists instead of the list ids
+// list_rank (optional): bins are the spatial ranks of the lists instead of the list ids; list_part (optional, with list_rank):
+// the probes vote for the key (placement_key.h).  qkey: [nq] scratch for the queries' keys when nq > 2048 -- written by the
+// histogram kernel, or, hist_ready, by whoever took the histogram (OrderHist)
 void launch_query_order(const int64_t* keys, int64_t nq, int nprobe, int nlist, int* hist,
                         int* qorder, hipStream_t s, const int* list_rank = nullptr, int* walk_part = nullptr, int* walk_state = nullptr,
-                        WalkSeed seed = WalkSeed(), bool run_walk_stat = true, bool hist_ready = false);
+                        WalkSeed seed = WalkSeed(), bool run_walk_stat = true, bool hist_ready = false,
+                        const uint8_t* list_part = nullptr, uint32_t* qkey = nullptr);
 // walk_part (optional): the walking-order statistic (32 counts, see launch_walk_stat) is computed along with the order when
 // run_walk_stat (otherwise the counts of an earlier search stay and the placement kernel freezes this launch's clock period)
 int walk_stat_samples(int64_t nq, int nprobe);

@@ -8,9 +8,13 @@
 //     live probe ahead; inside a list the next 256-code chunk is requested before the
 //     current one is consumed;
 //   * double-buffered LDS LUT, one workgroup barrier per probe;
-//   * workgroups are dealt to XCDs so that queries adjacent in `qorder` (sorted by
-//     nearest coarse centroid) share an L2: their term2 rows and list codes are then
-//     mostly L2 hits instead of fabric reads.  Placement only affects speed.  (Walking a
+//   * workgroups are dealt to XCDs so that queries adjacent in `qorder` share an L2: XCD x scans
+//     the x-th contiguous eighth of the queries sorted by placement_rank (placement_key.h).  A
+//     term2 row or a list's codes are an L2 hit only when another workgroup of the same XCD
+//     asked for the same list a few microseconds earlier, so the row hit rate is decided by
+//     how few distinct lists an XCD's chunk of queries probes: the key is the spatial rank of
+//     the list the query's PROBES vote for (the partition of neighbouring lists that holds most
+//     of them), not of its nearest list alone.  Placement only affects speed.  (Walking a
 //     query's probes in the spatial order of their lists as well was measured and does not
 //     pay: the nearest lists must come first to tighten the admission threshold.)
 #include <algorithm>
@@ -21,6 +25,7 @@
 #include "kernels.h"
 #include "scan_common.cuh"
 #include "scan16_common.cuh"
+#include "placement_key.h"
 #include "walk_order.cuh"
 #include "wave_topk.cuh"
 
@@ -812,25 +817,28 @@ bool launch_scan16(const ScanArgs& a, const ScanLaunch& L, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
-// query order: counting sort of the queries by their nearest coarse centroid
-// (keys[q][0]).  Order inside a bin is arbitrary -- it only influences which
+// query order: counting sort of the queries by placement_rank of their probes
+// (placement_key.h: the rank of the list the probes vote for; without list_part the
+// nearest list's).  The histogram kernel -- or the coarse stage's last kernel, OrderHist --
+// leaves every query's key in qkey[], and the placement sorts by that array: the two agree
+// by construction.  Order inside a bin is arbitrary -- it only influences which
 // workgroups run next to each other, never a result.
 // ---------------------------------------------------------------------------
 __global__ void qorder_hist_kernel(const int64_t* __restrict__ keys, int64_t nq, int nprobe,
                                    int nlist, int* __restrict__ hist, const int* __restrict__ list_rank,
-                                   int shift, int nbins) {
+                                   const uint8_t* __restrict__ list_part, uint32_t* __restrict__ qkey, int shift, int nbins) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
-    const int64_t k0 = keys[q * nprobe];
-    const bool ok = k0 >= 0 && k0 < nlist;
-    atomicAdd(&hist[ok ? ((list_rank ? list_rank[k0] : (int)k0) >> shift) : nbins - 1], 1);
+    const uint32_t r = placement_rank(keys + q * nprobe, nprobe, nlist, list_rank, list_part);
+    qkey[q] = r;            // the placement kernel sorts by exactly the key that was counted
+    atomicAdd(&hist[placement_bin(r, shift, nbins)], 1);
 }
 
 // prefix of the bin counts (every workgroup recomputes it in LDS: at most 16 Ki bins) + placement
-__global__ __launch_bounds__(256) void qorder_place_kernel(const int64_t* __restrict__ keys, int64_t nq, int nprobe,
-                                                           int nlist, const int* __restrict__ hist,
+__global__ __launch_bounds__(256) void qorder_place_kernel(const uint32_t* __restrict__ qkey, int64_t nq,
+                                                           const int* __restrict__ hist,
                                                            int* __restrict__ cnt, int* __restrict__ qorder,
-                                                           const int* __restrict__ list_rank, int shift, int nbins, int* walk_freeze) {
+                                                           int shift, int nbins, int* walk_freeze) {
     extern __shared__ int pre[];                 // [nbins] exclusive prefix
     // a search that does not re-sample the walking statistic still freezes this launch's clock period per XCD = the running
     // mean of the walk times measured so far (walk_stat_kernel does it otherwise)
@@ -858,9 +866,7 @@ __global__ __launch_bounds__(256) void qorder_place_kernel(const int64_t* __rest
     __syncthreads();
     const int64_t q = (int64_t)blockIdx.x * 256 + t;
     if (q >= nq) return;
-    const int64_t k0 = keys[q * nprobe];
-    const bool ok = k0 >= 0 && k0 < nlist;
-    const int bin = ok ? ((list_rank ? list_rank[k0] : (int)k0) >> shift) : nbins - 1;
+    const int bin = placement_bin(qkey[q], shift, nbins);     // (the key the histogram counted: placement_key.h)
     qorder[pre[bin] + atomicAdd(&cnt[bin], 1)] = (int)q;
 }
 
@@ -884,7 +890,8 @@ __device__ __forceinline__ int walk_stat_sample(const int64_t* __restrict__ keys
 
 __global__ __launch_bounds__(1024) void qorder_single_kernel(const int64_t* __restrict__ keys, int nq, int nprobe, int nlist,
                                                              int* __restrict__ qorder, const int* __restrict__ list_rank,
-                                                             int shift, int nbins, int* walk_freeze) {
+                                                             const uint8_t* __restrict__ list_part, int shift, int nbins,
+                                                             int* walk_freeze) {
     extern __shared__ int cnt[];                 // [nbins] counts, then running offsets
     if (walk_freeze && threadIdx.x < 8) {        // (see qorder_place_kernel)
         const int mean = walk_freeze[threadIdx.x * 16];
@@ -894,12 +901,16 @@ __global__ __launch_bounds__(1024) void qorder_single_kernel(const int64_t* __re
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     for (int b = t; b < nbins; b += 1024) cnt[b] = 0;
     __syncthreads();
-    auto bin_of = [&](int q) {
-        const int64_t k0 = keys[(int64_t)q * nprobe];
-        const bool ok = k0 >= 0 && k0 < nlist;
-        return ok ? ((list_rank ? list_rank[k0] : (int)k0) >> shift) : nbins - 1;
-    };
-    for (int q = t; q < nq; q += 1024) atomicAdd(&cnt[bin_of(q)], 1);
+    // a thread's (at most two) queries: the bins are computed once and kept for the placement
+    int mybin[2] = {0, 0};
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int q = t + u * 1024;
+        if (q < nq) {
+            mybin[u] = placement_bin(placement_rank(keys + (int64_t)q * nprobe, nprobe, nlist, list_rank, list_part), shift, nbins);
+            atomicAdd(&cnt[mybin[u]], 1);
+        }
+    }
     __syncthreads();
     // exclusive prefix: a thread owns `per` consecutive bins
     const int per = (nbins + 1023) / 1024;
@@ -920,7 +931,11 @@ __global__ __launch_bounds__(1024) void qorder_single_kernel(const int64_t* __re
     for (int i = 0; i < per; i++)
         if (b0 + i < nbins) { const int c = cnt[b0 + i]; cnt[b0 + i] = run; run += c; }
     __syncthreads();
-    for (int q = t; q < nq; q += 1024) qorder[atomicAdd(&cnt[bin_of(q)], 1)] = q;
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int q = t + u * 1024;
+        if (q < nq) qorder[atomicAdd(&cnt[mybin[u]], 1)] = q;
+    }
 }
 
 // at most 16 Ki bins (the prefix is recomputed per workgroup in LDS): many-list indexes are binned
@@ -934,7 +949,7 @@ void query_order_bins(int nlist, int* shift_out, int* nbins_out) {
 
 void launch_query_order(const int64_t* keys, int64_t nq, int nprobe, int nlist, int* hist,
                         int* qorder, hipStream_t s, const int* list_rank, int* walk_part, int* walk_state, WalkSeed seed, bool run_walk_stat,
-                        bool hist_ready) {
+                        bool hist_ready, const uint8_t* list_part, uint32_t* qkey) {
     if (nq <= 0) return;
     int shift, nbins;
     query_order_bins(nlist, &shift, &nbins);
@@ -942,7 +957,7 @@ void launch_query_order(const int64_t* keys, int64_t nq, int nprobe, int nlist, 
         const size_t smem1 = (size_t)nbins * sizeof(int);
         ensure_dynamic_lds(reinterpret_cast<const void*>(qorder_single_kernel), smem1);
         hipLaunchKernelGGL(qorder_single_kernel, dim3(1), dim3(1024), smem1, s, keys, (int)nq, nprobe, nlist, qorder, list_rank,
-                           shift, nbins, (walk_part && !run_walk_stat) ? walk_state : nullptr);
+                           list_part, shift, nbins, (walk_part && !run_walk_stat) ? walk_state : nullptr);
         // (the statistic inside this one-workgroup kernel was measured: 8192 samples on one CU cost 36 us against 5)
         if (walk_part && nq >= 2 && run_walk_stat) launch_walk_stat(keys, qorder, nq, nprobe, walk_part, walk_state, s, seed);
         return;
@@ -952,12 +967,12 @@ void launch_query_order(const int64_t* keys, int64_t nq, int nprobe, int nlist, 
     if (!hist_ready) {          // (otherwise the coarse stage's last kernel left the counts: OrderHist, kernels.h)
         (void)hipMemsetAsync(hist, 0, 2 * stride * sizeof(int), s);
         hipLaunchKernelGGL(qorder_hist_kernel, dim3(g), dim3(256), 0, s, keys, nq, nprobe, nlist, hist, list_rank,
-                           shift, nbins);
+                           list_part, qkey, shift, nbins);
     }
     const size_t smem = (size_t)nbins * sizeof(int);
     ensure_dynamic_lds(reinterpret_cast<const void*>(qorder_place_kernel), smem);
-    hipLaunchKernelGGL(qorder_place_kernel, dim3(g), dim3(256), smem, s, keys, nq, nprobe, nlist, hist,
-                       hist + stride, qorder, list_rank, shift, nbins, (walk_part && !run_walk_stat) ? walk_state : nullptr);
+    hipLaunchKernelGGL(qorder_place_kernel, dim3(g), dim3(256), smem, s, qkey, nq, hist,
+                       hist + stride, qorder, shift, nbins, (walk_part && !run_walk_stat) ? walk_state : nullptr);
     if (walk_part && run_walk_stat) launch_walk_stat(keys, qorder, nq, nprobe, walk_part, walk_state, s, seed);
 }
 

@@ -70,6 +70,7 @@ struct ScanPlan {
     QueryOrder order = QueryOrder::none;
     bool order_hist_ready = false;   // QueryOrder::walk: the coarse stage may have left the histogram (the page is the whole call)
     bool order_by_rank = false;      // bins are the lists' spatial ranks
+    bool order_vote = false;         // ... of the list the query's probes vote for (placement_key.h), not of its nearest list
     int walk_first = -1;         // ScanArgs::walk_first
     bool walk_auto = false;      // the walking order is decided from the walk statistic (not forced by VLQ_WALK_FIRST)
     bool walk_limit_full = false;    // the list-id order whatever the statistic says (limit = every sample), else VLQ_WALK_SHARE
@@ -218,6 +219,9 @@ inline ScanPlan plan_scan(const ScanShape& s) {
         if (!orderable) return;
         p.order = QueryOrder::walk;
         p.order_by_rank = s.have_rank && s.imi_nbits == 0;
+        // which queries share an XCD decides the table-row hit rate: the pages that take the walk order
+        // sort by the vote of the probes; the float16-table pages (QueryOrder::plain) keep the rank of the nearest list
+        p.order_vote = p.order_by_rank;
         p.order_hist_ready = s.ni == s.n;
     };
     L.imi = s.imi_nbits > 0;
