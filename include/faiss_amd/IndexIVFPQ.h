@@ -104,6 +104,7 @@ struct IndexIVFPQ : IndexIVF {
   /// precompute_table (IndexIVFPQ.cpp:392-459), flat-L2 quantizer: table type 1,
   /// computed on the device and mirrored into `precomputed_table`
   void precompute_table() {
+    if (metric_type == METRIC_INNER_PRODUCT) return;   // IndexIVFPQ.cpp:397-401: not needed for inner product quantizers
     const MultiIndexQuantizer* miq = dynamic_cast<const MultiIndexQuantizer*>(quantizer);
     if (use_precomputed_table == 0)      // choose the type of table (IndexIVFPQ.cpp:396-408)
       use_precomputed_table = (miq && pq.M % miq->pq.M == 0) ? 2 : 1;
@@ -343,8 +344,12 @@ struct IndexIVFPQ : IndexIVF {
   void sync_(bool with_lists) const {
     const IndexFlat* flat = dynamic_cast<const IndexFlat*>(quantizer);
     const MultiIndexQuantizer* miq = dynamic_cast<const MultiIndexQuantizer*>(quantizer);
-    FAISS_THROW_IF_NOT_MSG((flat && flat->metric_type == METRIC_L2) || miq,
-                           "coarse quantizer must be an IndexFlatL2 or a MultiIndexQuantizer");
+    if (metric_type == METRIC_INNER_PRODUCT)   // (a multi-index quantizer has no reconstruct: IndexIVFPQ.cpp:613 would throw)
+      FAISS_THROW_IF_NOT_MSG(flat && flat->metric_type == METRIC_INNER_PRODUCT,
+                             "METRIC_INNER_PRODUCT needs an IndexFlatIP coarse quantizer (a MultiIndexQuantizer is not served)");
+    else
+      FAISS_THROW_IF_NOT_MSG((flat && flat->metric_type == METRIC_L2) || miq,
+                             "coarse quantizer must be an IndexFlatL2 or a MultiIndexQuantizer");
     if (!h_) {
       VLQ_CHECK(vlq_ivfpq_create(&h_, device, d, (int)nlist, (int)pq.M, (int)pq.nbits));
       hdirty_ = ldirty_ = true;
@@ -356,6 +361,7 @@ struct IndexIVFPQ : IndexIVF {
       VLQ_CHECK(vlq_ivfpq_set_pq_centroids(h_, pq.centroids.data()));
       hdirty_ = false;
     }
+    VLQ_CHECK(vlq_ivfpq_set_metric(h_, (int)metric_type));
     VLQ_CHECK(vlq_ivfpq_set_search_options(h_, by_residual, by_residual ? (use_precomputed_table ? 1 : 0) : 0,
                                            (int64_t)max_codes));
     // polysemous_ht > 0 (IndexIVFPQ.cpp:1023-1025): the filtered scan.  By residual over a flat quantizer the code of the

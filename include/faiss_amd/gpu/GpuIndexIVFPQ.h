@@ -43,7 +43,7 @@ class GpuIndex : public faiss::Index {
   GpuIndex(GpuResources* resources, int dims, faiss::MetricType metric, GpuIndexConfig config)
       : Index(dims, metric), resources_(resources), device_(config.device), memorySpace_(config.memorySpace) {
     FAISS_THROW_IF_NOT_MSG(resources_, "null GpuResources");
-    FAISS_THROW_IF_NOT_MSG(metric == METRIC_L2, "only METRIC_L2 is built");
+    FAISS_THROW_IF_NOT_MSG(metric == METRIC_L2 || metric == METRIC_INNER_PRODUCT, "unknown metric");
     resources_->initializeForDevice(device_);
   }
   int getDevice() const { return device_; }
@@ -84,6 +84,7 @@ class GpuIndexIVFPQ : public GpuIndex {
         w1_(1), ivfpqConfig_(config), nlist_(nlist), nprobe_(1), subQuantizers_(subQuantizers),
         bitsPerCode_(bitsPerCode), reserveMemoryVecs_(0) {
     verifyConfig_();
+    FAISS_THROW_IF_NOT_MSG(metric == METRIC_L2, "the VLQ index is built for METRIC_L2 only");
     FAISS_THROW_IF_NOT_MSG(bitsPerCode_ >= 1 && bitsPerCode_ <= 8, "Bits per code must be <= 8");
     FAISS_THROW_IF_NOT_MSG(dims % subQuantizers_ == 0, "Number of sub-quantizers must be an even divisor of the dimensions");
     is_trained = false;
@@ -118,8 +119,13 @@ class GpuIndexIVFPQ : public GpuIndex {
     FAISS_THROW_IF_NOT_MSG(index->by_residual, "GPU: only by_residual = true is supported");
     FAISS_THROW_IF_NOT_MSG(index->polysemous_ht >= 0, "GPU: polysemous_ht < 0");
     const IndexFlat* flat = dynamic_cast<const IndexFlat*>(index->quantizer);
-    FAISS_THROW_IF_NOT_MSG(flat && flat->metric_type == METRIC_L2,
-                           "Only IndexFlatL2 is supported as the coarse quantizer (gpu/GpuIndexIVF.cu:131-133)");
+    // gpu/GpuIndexIVF.cu:131-133 takes IndexFlatL2 and IndexFlatIP; the quantizer's metric is the index's
+    FAISS_THROW_IF_NOT_MSG(flat && (flat->metric_type == METRIC_L2 || flat->metric_type == METRIC_INNER_PRODUCT) &&
+                               flat->metric_type == index->metric_type,
+                           "Only IndexFlatL2 / IndexFlatIP with the index's own metric is supported as the coarse quantizer");
+    // under inner product the library has no polysemous filter (include/vlq_ivfpq.h)
+    FAISS_THROW_IF_NOT_MSG(index->metric_type == METRIC_L2 || index->polysemous_ht == 0,
+                           "GPU: polysemous_ht > 0 with METRIC_INNER_PRODUCT is not served");
     d = index->d; metric_type = index->metric_type;
     nlist_ = (int)index->nlist; nprobe_ = (int)index->nprobe;
     subQuantizers_ = (int)index->pq.M; bitsPerCode_ = (int)index->pq.nbits;
@@ -156,6 +162,7 @@ class GpuIndexIVFPQ : public GpuIndex {
     FAISS_THROW_IF_NOT_MSG(ivfpqConfig_.indicesOptions != INDICES_IVF, "Cannot copy to CPU as GPU index doesn't retain indices (INDICES_IVF)");
     IndexFlat* flat = dynamic_cast<IndexFlat*>(index->quantizer);
     FAISS_THROW_IF_NOT_MSG(flat, "target quantizer must be an IndexFlat");
+    FAISS_THROW_IF_NOT_MSG(flat->metric_type == metric_type, "target quantizer must have the index's metric (IndexFlatL2 / IndexFlatIP)");
     index->d = d; index->metric_type = metric_type; index->is_trained = is_trained;
     index->nlist = nlist_; index->nprobe = nprobe_; index->ntotal = ntotal;
     index->by_residual = true; index->use_precomputed_table = 0;
@@ -171,7 +178,7 @@ class GpuIndexIVFPQ : public GpuIndex {
       index->ids[i] = getListIndices(i);
       index->codes[i] = getListCodes(i);
     }
-    if (usePrecomputed_) index->precompute_table();
+    if (usePrecomputed_) index->precompute_table();   // (returns at once under inner product, as the reference's does)
   }
 
   void reserveMemory(size_t numVecs) {
@@ -217,8 +224,9 @@ class GpuIndexIVFPQ : public GpuIndex {
   void train(Index::idx_t n, const float* x) override {
     if (is_trained) return;
     if (line_) { trainVLQ_(n, x); return; }
-    faiss::IndexFlatL2 flat(d);
+    faiss::IndexFlat flat(d, metric_type);   // IndexFlatL2 / IndexFlatIP are this class with the metric set
     faiss::IndexIVFPQ cpu(&flat, d, nlist_, subQuantizers_, bitsPerCode_);
+    cpu.metric_type = metric_type;
 #ifndef VLQ_WITH_REFERENCE_FAISS
     flat.device = device_;   // our CPU-named classes train on the device too
     cpu.device = device_;
@@ -496,11 +504,13 @@ class GpuIndexIVFPQ : public GpuIndex {
   void create_() {
     VLQ_CHECK(vlq_ivfpq_create(&h_, device_, d, nlist_, subQuantizers_, bitsPerCode_));
     VLQ_CHECK(vlq_ivfpq_set_stream(h_, (void*)resources_->getDefaultStream(device_)));
+    VLQ_CHECK(vlq_ivfpq_set_metric(h_, (int)metric_type));   // before any list arrives: no term 2 is built under inner product
     usePrecomputed_ = ivfpqConfig_.usePrecomputedTables;
     VLQ_CHECK(vlq_ivfpq_set_search_options(h_, 1, usePrecomputed_ ? 1 : 0, 0));
     // useFloat16LookupTables: half tables for 16 x 8-bit codes with precomputed tables, built as the reference
-    // builds them (vlq_ivfpq_set_float16_tables); other shapes compute in fp32 (superset precision)
-    if (ivfpqConfig_.useFloat16LookupTables && subQuantizers_ == 16 && bitsPerCode_ == 8) {
+    // builds them (vlq_ivfpq_set_float16_tables); other shapes compute in fp32 (superset precision).  The library has no
+    // half tables under inner product: the hint is dropped there and the fp32 table serves
+    if (ivfpqConfig_.useFloat16LookupTables && subQuantizers_ == 16 && bitsPerCode_ == 8 && metric_type == METRIC_L2) {
       VLQ_CHECK(vlq_ivfpq_set_float16_tables(h_, 1));
       fp16TablesOn_ = true;
     }

@@ -1,6 +1,7 @@
 // write_index / read_index for the index types on the hot path, in the reference's
 // on-disk format (index_io.cpp:226-317, :459-532, :536-680): fourcc + header, nested
 // quantizer, per-list id and code vectors.
+//   "IxFI"  IndexFlatIP
 //   "IxF2"  IndexFlatL2            "Imiq"  MultiIndexQuantizer        "IvPQ"  IndexIVFPQ
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
@@ -76,8 +77,7 @@ inline void read_pq(ProductQuantizer& pq, FILE* f) {
 inline void write_index(const Index* idx, FILE* f) {
   using namespace io_detail;
   if (const IndexFlat* flat = dynamic_cast<const IndexFlat*>(idx)) {
-    FAISS_THROW_IF_NOT_MSG(flat->metric_type == METRIC_L2, "only IndexFlatL2 is on the path");
-    w1(f, fourcc("IxF2"));
+    w1(f, fourcc(flat->metric_type == METRIC_L2 ? "IxF2" : "IxFI"));     // index_io.cpp:166-171
     write_header(idx, f);
     wvec(f, flat->xb);
   } else if (const MultiIndexQuantizer* miq = dynamic_cast<const MultiIndexQuantizer*>(idx)) {
@@ -114,6 +114,13 @@ inline Index* read_index(FILE* f, bool precompute = true) {
   using namespace io_detail;
   uint32_t h;
   r1(f, h);
+  if (h == fourcc("IxFI")) {
+    std::unique_ptr<IndexFlatIP> flat(new IndexFlatIP());
+    read_header(flat.get(), f);
+    rvec(f, flat->xb);
+    FAISS_THROW_IF_NOT(flat->xb.size() == (size_t)flat->ntotal * flat->d);
+    return flat.release();
+  }
   if (h == fourcc("IxF2")) {
     std::unique_ptr<IndexFlatL2> flat(new IndexFlatL2());
     read_header(flat.get(), f);

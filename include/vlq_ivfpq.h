@@ -9,7 +9,8 @@
  *
  * Conventions (Index.h:25-36, :62): vectors are row-major float32 x[i*d+j];
  * labels are int64; results are ascending squared-L2 distances; missing results
- * are label -1 / distance FLT_MAX (Heap.h:76-78,318-321).
+ * are label -1 / distance FLT_MAX (Heap.h:76-78,318-321).  With vlq_ivfpq_set_metric(h, 0):
+ * descending inner products, missing results -1 / -FLT_MAX.
  *
  * Pointers marked [h|d] may be host or device memory (the reference accepts
  * either, gpu/utils/CopyUtils.cuh); device pointers must belong to the index's
@@ -255,6 +256,39 @@ int vlq_ivfpq_query_codes(vlq_ivfpq_t h, int64_t n, const float* x, const int64_
 /* indexIVFPQ_stats.n_hamming_pass (IndexIVFPQ.h:169-195, IndexIVFPQ.cpp:902, :1048): codes that passed the filter since the
  * last reset.  Synchronises the stream, like vlq_ivfpq_stats. */
 int vlq_ivfpq_polysemous_stats(vlq_ivfpq_t h, uint64_t* n_hamming_pass, int reset);
+
+/* ---- Inner-product metric: IndexIVFPQ with metric_type = METRIC_INNER_PRODUCT over an IndexFlatIP quantizer (what
+ * index_factory(d, "IVF..,PQ..", METRIC_INNER_PRODUCT) builds, AutoTune.cpp:695,759; the IP branch of InvertedListScanner,
+ * IndexIVFPQ.cpp:540-555, :609-624, :1039-1042).  metric is the reference's MetricType (Index.h): 0 = inner product, 1 = L2 (the
+ * default).  May be called at any time: lists and quantizers stay.  A handle whose metric is L2 -- never switched, or switched
+ * to inner product and back -- behaves exactly as before.
+ *
+ * Under inner product:
+ *   scan     the per-query table is -compute_inner_prod_table(q) (:548-555), used for every list whatever use_precomputed_table
+ *            says (accepted and ignored; precompute_table only warns, :397-401); per list dis0 = -fvec_inner_product(q,
+ *            centroid, d) by_residual (:609-616 -- the coarse_dis handed to vlq_ivfpq_search_preassigned is NOT used), 0
+ *            otherwise; a code's dis0 + tab[0][c0] + ... left to right is admitted if below the heap top (:786-800); key < 0,
+ *            empty lists, max_codes (counted in list sizes), store_pairs, the key >= nlist error and the ncode of
+ *            vlq_ivfpq_stats are as for L2.  After the reorder every value is negated (:1039-1042): D rows are DESCENDING
+ *            inner products, a missing result is label -1 / distance -FLT_MAX.
+ *   coarse   vlq_ivfpq_coarse_search = IndexFlat::search with a min-heap -> knn_inner_product (IndexFlat.cpp:47-50,
+ *            utils.cpp:726-755, :790-829): the nprobe largest inner products, descending, coarse_dis = the inner product; at
+ *            a tie the lower centroid id comes first, and stays at the boundary.  The float16 screen is an L2 bound: off
+ *            (vlq_ivfpq_coarse_screen_state reports enabled = 0).
+ *   add      vlq_ivfpq_add / vlq_ivfpq_encode assign to the FIRST maximum (quantizer->assign); residuals and codes as for L2
+ *            (IndexIVFPQ.cpp:192-272).  vlq_ivfpq_encode_preassigned and vlq_ivfpq_query_tables(inner_product = 1) are
+ *            unchanged (the negation is the scan's).
+ *   term 2   IndexIVFPQ::precomputed_table is neither built nor kept: vlq_ivfpq_get_precomputed_table returns VLQ_ERR_STATE.
+ * VLQ_ERR_UNSUPPORTED under inner product, from the search / add / encode call that meets the combination: a multi-index
+ * quantizer (the reference cannot reconstruct a centroid from one, :613), float16 tables, vlq_ivfpq_set_polysemous_ht > 0,
+ * vlq_ivfpq_set_refine_pq / vlq_ivfpq_refine / the vlq_ivfpq_search_refined calls, more than VLQ_MAX_NPROBE probes.
+ * One limit is the scan kernel's own: its workgroup keeps the table (M * ksub * 4 bytes), the query (4 * d), 24 bytes per probe
+ * and 2 KB of queues in LDS, 160 KB at the most.  vlq_ivfpq_create admits tables up to 144 KB, so an index near that size (M
+ * about 130 .. 144 at 8 bits) with several hundred probes, which L2 serves, returns VLQ_ERR_UNSUPPORTED from the search call
+ * under inner product; the message names M, ksub, nprobe, k and d.
+ * vlq_ivfpq_set_scan_schedule is ignored (one kernel serves the metric, csrc/scan_ip.hip). */
+int vlq_ivfpq_set_metric(vlq_ivfpq_t h, int metric);
+int vlq_ivfpq_get_metric(vlq_ivfpq_t h, int* metric);
 
 /* Merge of per-shard results for indexes whose inverted lists are split over GPUs / ranks
  * (GpuIndexIVFPQ::merge, gpu/GpuIndexIVFPQ.cu:1467-1591, used by gpu/test/deep1b16_query.cpp

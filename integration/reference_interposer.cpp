@@ -18,8 +18,11 @@
 //
 // The host-side ids / codes vectors stay the authoritative copy (write_index, copy_subset_to, IndexIVFPQR's
 // refinement read them); they are mirrored to HBM, list-contiguously, before the first search after a change.
-// What the device path does not cover (inner-product metric, polysemous filtering by residual over a flat quantizer, on-the-fly scan threshold,
-// BLAS-encoded sub-vectors of >= 16 dimensions, nbits > 8) is handed to the reference's own definition (dlsym RTLD_NEXT).
+// An index with metric_type = METRIC_INNER_PRODUCT over an IndexFlatIP is served too (vlq_ivfpq_set_metric): search_knn_with_key,
+// search and add_core_o; its precompute_table does nothing, as in the reference.
+// What the device path does not cover (polysemous filtering by residual over a flat quantizer, on-the-fly scan threshold,
+// BLAS-encoded sub-vectors of >= 16 dimensions, nbits > 8; under inner product also a multi-index quantizer, any polysemous_ht > 0
+// and more than VLQ_MAX_NPROBE probes) is handed to the reference's own definition (dlsym RTLD_NEXT).
 //
 // Two conveniences for running the drivers where /home/data does not exist: fopen() and open() of a path
 // below /home/data/ are redirected below $VLQ_DATA_ROOT when that variable is set.  At exit a one-line
@@ -115,10 +118,12 @@ uint64_t sig_floats(uint64_t h, const float* p, size_t n) {
     return mix(mix(h, u), n);
 }
 
-const faiss::IndexFlat* flat_l2(const faiss::IndexIVFPQ* ix) {
+// the flat quantizer of the index's own metric: IndexFlatL2 under METRIC_L2, IndexFlatIP under METRIC_INNER_PRODUCT
+const faiss::IndexFlat* flat_q(const faiss::IndexIVFPQ* ix) {
     const faiss::IndexFlat* f = dynamic_cast<const faiss::IndexFlat*>(ix->quantizer);
-    return (f && f->metric_type == faiss::METRIC_L2) ? f : nullptr;
+    return (f && f->metric_type == ix->metric_type) ? f : nullptr;
 }
+bool is_ip(const faiss::IndexIVFPQ* ix) { return ix->metric_type == faiss::METRIC_INNER_PRODUCT; }
 const faiss::MultiIndexQuantizer* imi2(const faiss::IndexIVFPQ* ix) {
     const faiss::MultiIndexQuantizer* m = dynamic_cast<const faiss::MultiIndexQuantizer*>(ix->quantizer);
     return (m && m->pq.M == 2 && m->pq.byte_per_idx <= 2 && ((size_t)1 << (2 * m->pq.nbits)) == ix->nlist) ? m : nullptr;
@@ -129,10 +134,12 @@ bool device_shape(const faiss::IndexIVFPQ* ix) {
     // VLQ_INTERPOSE=off: every call goes to the reference's own definition -- the CPU-only run of the SAME binary
     static const bool off = getenv("VLQ_INTERPOSE") && strcmp(getenv("VLQ_INTERPOSE"), "off") == 0;
     if (off) return false;
-    if (ix->metric_type != faiss::METRIC_L2 || !ix->quantizer) return false;
+    if ((ix->metric_type != faiss::METRIC_L2 && !is_ip(ix)) || !ix->quantizer) return false;
     if (ix->pq.byte_per_idx != 1 || ix->pq.nbits > 8) return false;
     if (ix->quantizer->ntotal != (faiss::Index::idx_t)ix->nlist) return false;
-    return flat_l2(ix) || imi2(ix);
+    // inner product: a flat quantizer only (the reference cannot reconstruct from a multi-index, IndexIVFPQ.cpp:613)
+    if (is_ip(ix)) return flat_q(ix) != nullptr;
+    return flat_q(ix) || imi2(ix);
 }
 
 // polysemous_ht > 0 on the device: the modes where the library's code of the query IS the reference's -- not by_residual
@@ -142,6 +149,7 @@ bool device_shape(const faiss::IndexIVFPQ* ix) {
 // (include/vlq_ivfpq.h), so those calls keep the reference's own definition and a caller of the reference's classes sees no change.
 bool poly_ok(const faiss::IndexIVFPQ* ix) {
     if (ix->polysemous_ht == 0) return true;
+    if (is_ip(ix)) return false;       // no filter under inner product on the device (include/vlq_ivfpq.h)
     if (ix->polysemous_ht < 0 || ix->pq.M % 4 != 0 || ix->pq.M > 64 || ix->nprobe > VLQ_MAX_NPROBE) return false;
     return !ix->by_residual || (ix->use_precomputed_table == 2 && imi2(ix) != nullptr);
 }
@@ -162,8 +170,10 @@ State& sync(const faiss::IndexIVFPQ* ix, bool with_lists) {
         st.lists_dirty = true;
         st.d = ix->d; st.nlist = ix->nlist; st.M = (int)ix->pq.M; st.nbits = (int)ix->pq.nbits;
     }
-    const faiss::IndexFlat* fl = flat_l2(ix);
-    const faiss::MultiIndexQuantizer* mi = imi2(ix);
+    const faiss::IndexFlat* fl = flat_q(ix);
+    const faiss::MultiIndexQuantizer* mi = fl ? nullptr : imi2(ix);
+    // (before the lists: no term 2 is built or kept while the metric is inner product)
+    check(vlq_ivfpq_set_metric(st.h, (int)ix->metric_type), "vlq_ivfpq_set_metric");
     uint64_t s = mix(1, ix->nlist);
     s = fl ? sig_floats(s, fl->xb.data(), fl->xb.size()) : sig_floats(s, mi->pq.centroids.data(), mi->pq.centroids.size());
     s = sig_floats(s, ix->pq.centroids.data(), ix->pq.centroids.size());
@@ -223,7 +233,8 @@ namespace faiss {
 void IndexIVFPQ::search_knn_with_key(size_t nx, const float* qx, const long* keys, const float* coarse_dis,
                                      float_maxheap_array_t* res, bool store_pairs) const {
     KnnTimer knn_timer;
-    const bool on_device = device_shape(this) && poly_ok(this) && scan_table_threshold == 0 &&
+    // (under inner product the library takes at most VLQ_MAX_NPROBE probes: include/vlq_ivfpq.h)
+    const bool on_device = device_shape(this) && poly_ok(this) && scan_table_threshold == 0 && !(is_ip(this) && nprobe > VLQ_MAX_NPROBE) &&
                            res->k >= 1 && res->k <= VLQ_MAX_K && (nprobe <= VLQ_MAX_NPROBE || (max_codes == 0 && nprobe <= 64 * VLQ_MAX_NPROBE)) &&
                            !(imi2(this) && by_residual && use_precomputed_table == 0);
     if (!on_device) {
@@ -310,16 +321,17 @@ void IndexIVFPQ::add_core_o(idx_t n, const float* x, const long* xids, float* re
 
 // IndexIVFPQ::search (IndexIVFPQ.cpp:1063-1081: quantizer->search, then search_knn_with_key) served whole: the coarse stage runs
 // on the device too and the probe lists (n x nprobe keys and distances: 246 MB for 10 000 queries at the multi-index drivers'
-// nprobe = 2048) stay in HBM.  A flat quantizer's coarse distances are the reference's to rounding (its sgemm's order is the BLAS
+// nprobe = 2048) stay in HBM.  A flat quantizer's coarse distances (inner products under that metric) are the reference's to rounding (its sgemm's order is the BLAS
 // vendor's: SURVEY.md 8c); a multi-index quantizer's cells are MinSumK's, replayed (csrc/imi_wide.hip).  VLQ_INTERPOSE_SEARCH=0
 // keeps the reference's own body (its quantizer->search, then the interposed search_knn_with_key).
 void IndexIVFPQ::search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const {
     static const bool whole_off = getenv("VLQ_INTERPOSE_SEARCH") && strcmp(getenv("VLQ_INTERPOSE_SEARCH"), "0") == 0;
     const MultiIndexQuantizer* mi = device_shape(this) ? imi2(this) : nullptr;
-    const IndexFlat* fl = device_shape(this) ? flat_l2(this) : nullptr;
+    const IndexFlat* fl = device_shape(this) ? flat_q(this) : nullptr;
     // (the quantizer's own search() must be the one replaced: a subclass may override it)
     const bool plain_quantizer = quantizer && ((mi && typeid(*quantizer) == typeid(MultiIndexQuantizer)) ||
-                                               (fl && (typeid(*quantizer) == typeid(IndexFlatL2) || typeid(*quantizer) == typeid(IndexFlat))));
+                                               (fl && (typeid(*quantizer) == typeid(IndexFlatL2) || typeid(*quantizer) == typeid(IndexFlatIP) ||
+                                                       typeid(*quantizer) == typeid(IndexFlat))));
     const bool on_device = !whole_off && plain_quantizer && poly_ok(this) && scan_table_threshold == 0 && k >= 1 && k <= VLQ_MAX_K &&
                            nprobe >= 1 && (mi ? (nprobe <= VLQ_MAX_IMI_NPROBE && (nprobe <= VLQ_MAX_NPROBE || max_codes == 0)) : nprobe <= VLQ_MAX_NPROBE) &&
                            nprobe <= nlist && !(mi && by_residual && use_precomputed_table == 0);
@@ -377,6 +389,12 @@ void MultiIndexQuantizer::search(idx_t n, const float* x, idx_t k, float* distan
 }
 
 void IndexIVFPQ::precompute_table() {
+    if (is_ip(this) && flat_q(this)) {   // IndexIVFPQ.cpp:397-401: the reference's own warning and return; nothing to compute
+        typedef void (*fn_t)(IndexIVFPQ*);
+        static fn_t ref = next_definition<fn_t>("_ZN5faiss10IndexIVFPQ16precompute_tableEv");
+        ref(this);
+        return;
+    }
     if (!(device_shape(this) && by_residual)) {
         typedef void (*fn_t)(IndexIVFPQ*);
         static fn_t ref = next_definition<fn_t>("_ZN5faiss10IndexIVFPQ16precompute_tableEv");

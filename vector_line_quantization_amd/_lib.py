@@ -22,6 +22,7 @@ SYMBOLS = [
     "vlq_ivfpq_set_refine_pq", "vlq_ivfpq_set_refine_codes", "vlq_ivfpq_get_list_refine_codes", "vlq_ivfpq_refine",
     "vlq_ivfpq_search_refined", "vlq_ivfpq_search_refined_preassigned",
     "vlq_ivfpq_set_polysemous_ht", "vlq_ivfpq_query_codes", "vlq_ivfpq_polysemous_stats",
+    "vlq_ivfpq_set_metric", "vlq_ivfpq_get_metric",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",

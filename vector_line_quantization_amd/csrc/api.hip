@@ -73,6 +73,7 @@ void drain_profile(vlq_ivfpq_t h) {
 }
 
 int ensure_term2(vlq_ivfpq_t h) {
+    if (h->metric == 0) return VLQ_OK;        // inner product: the table depends on the query only, term 2 is never built
     if (!(h->by_residual && h->use_precomputed_table == 1)) return VLQ_OK;
     if (h->term2_valid) return VLQ_OK;
     if (!h->have_coarse || !h->have_pq) return fail(VLQ_ERR_STATE, "centroids not set");
@@ -267,6 +268,48 @@ int coarse_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float*
     return VLQ_OK;
 }
 
+// Coarse stage of one page under the inner-product metric: IndexFlat::search with a min-heap -> knn_inner_product
+// (IndexFlat.cpp:47-50, utils.cpp:726-755, :790-829): the nprobe largest inner products, descending, a later column replaces
+// a kept one only if strictly larger (the lower id stays at a tie).  The f32 MFMA distance kernel with zero norms gives
+// (0 + 0) - 2 <q, c> exactly, the (distance, column) selections run over that, launch_coarse_ip_finish turns the kept values
+// back into inner products.  The float16 screen and the filtered stage are L2 bounds: not used here.
+static int coarse_page_ip(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev, int64_t* keys_dev) {
+    TRY(h->ws_qn.reserve((size_t)n * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(h->ws_qn.p, 0, (size_t)n * sizeof(float), h->stream));
+    if (!h->czero.p) {
+        TRY(h->czero.reserve((size_t)h->nlist * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(h->czero.p, 0, (size_t)h->nlist * sizeof(float), h->stream));
+    }
+    const bool argmin = nprobe == 1 && vlq::coarse_argmin_ok(h->nlist, h->d);
+    const int64_t n_pad = (n + 127) / 128 * 128;
+    float* tmin = nullptr;
+    if (argmin) {
+        TRY(h->ws_tmin.reserve((size_t)n * (h->nlist / 64) * 8));
+        tmin = h->ws_tmin.as<float>();
+    } else {
+        TRY(h->ws_dist.reserve((size_t)n_pad * h->nlist * sizeof(float)));
+        if (vlq::coarse_tile_minima_ok(h->nlist, h->d, nprobe)) {
+            TRY(h->ws_tmin.reserve((size_t)n * (h->nlist / 64) * sizeof(float)));
+            tmin = h->ws_tmin.as<float>();
+        }
+    }
+    vlq::launch_coarse_distances(x_dev, h->coarse.as<float>(), h->ws_qn.as<float>(), h->czero.as<float>(),
+                                 argmin ? nullptr : h->ws_dist.as<float>(), n, h->nlist, h->d, h->stream, tmin, argmin ? 0 : n_pad);
+    if (argmin) vlq::launch_coarse_argmin(tmin, n, h->nlist, cdis_dev, keys_dev, h->stream);
+    else vlq::launch_coarse_select(h->ws_dist.as<float>(), n, h->nlist, nprobe, cdis_dev, keys_dev, h->stream, tmin);
+    vlq::launch_coarse_ip_finish(cdis_dev, keys_dev, n * nprobe, h->stream);
+    HIP_TRY(hipGetLastError());
+    return VLQ_OK;
+}
+
+// what the inner-product metric does not serve (include/vlq_ivfpq.h)
+static int ip_unsupported(vlq_ivfpq_t h) {
+    if (h->imi_nbits > 0)
+        return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric with a multi-index quantizer is not built (the reference cannot reconstruct "
+                    "a centroid from one, IndexIVFPQ.cpp:613)");
+    return VLQ_OK;
+}
+
 // coarse stage on device buffers: x_dev [n][d] -> cdis_dev, keys_dev [n][nprobe]
 // MultiIndexQuantizer::search (IndexPQ.cpp:804-857) for one page: the two distance tables,
 // their T smallest entries in order, then the MinSumK walk
@@ -413,6 +456,17 @@ int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* cdis_de
 
 int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev,
                int64_t* keys_dev) {
+    if (h->metric == 0) {
+        TRY(ip_unsupported(h));
+        StageTimer tm(h, 0);
+        const int64_t page = (nprobe == 1 && vlq::coarse_argmin_ok(h->nlist, h->d)) ? 32768 : query_page(h);
+        for (int64_t i0 = 0; i0 < n; i0 += page) {
+            const int64_t ni = std::min(page, n - i0);
+            TRY(coarse_page_ip(h, ni, x_dev + i0 * h->d, nprobe, cdis_dev + i0 * nprobe, keys_dev + i0 * nprobe));
+        }
+        tm.stop();
+        return VLQ_OK;
+    }
     StageTimer tm(h, 0);
     if (h->imi_nbits > 0) {
         const int64_t kc = int64_t(1) << h->imi_nbits;
@@ -508,9 +562,60 @@ int scan_poly_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* k
     return VLQ_OK;
 }
 
+// Inner-product metric (vlq_ivfpq_set_metric(h, 0)): one kernel serves it (scan_ip.hip), chosen before the scan plan is
+// consulted.  No per-query table pass and no term 2: the kernel builds its table from the codebook.
+int scan_ip_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev, const float* cdis_dev, int nprobe, int k,
+                float* D_dev, int64_t* I_dev, int store_pairs) {
+    TRY(ip_unsupported(h));
+    if (h->fp16_tables) return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric with float16 look-up tables is not built");
+    if (h->polysemous_ht > 0) return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric with polysemous filtering (polysemous_ht = %d) is not built", h->polysemous_ht);
+    if (nprobe > vlq::kIpMaxProbes)
+        return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric with nprobe=%d > %d is not built", nprobe, vlq::kIpMaxProbes);
+    if (!vlq::ip_shape_ok(h->M, h->ksub, nprobe, k, h->d))
+        return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric: M=%d x %d entries, nprobe=%d, k=%d, d=%d exceed the scan's LDS", h->M, h->ksub, nprobe, k, h->d);
+    const int64_t page = 32768;
+    for (int64_t i0 = 0; i0 < n; i0 += page) {
+        const int64_t ni = std::min(page, n - i0);
+        vlq::ScanArgs a;
+        a.codes = h->codes.as<uint8_t>();
+        a.ids = h->ids.as<int64_t>();
+        a.list_off = h->list_off.as<int64_t>();
+        a.list_len = h->list_len.as<int64_t>();
+        a.term2 = nullptr;
+        a.qtab = nullptr;
+        a.queries = x_dev + i0 * h->d;
+        a.coarse = h->coarse.as<float>();
+        a.pq_cent = h->pq.as<float>();
+        a.pq_cent_t = h->pq_t.as<float>();
+        a.keys = keys_dev + i0 * nprobe;
+        a.coarse_dis = cdis_dev + i0 * nprobe;
+        a.D = D_dev + i0 * k;
+        a.I = I_dev + i0 * k;
+        a.ncode = h->stats.as<unsigned long long>();
+        a.bad_key = reinterpret_cast<int*>(h->stats.as<unsigned long long>() + 1);
+        a.nq = ni;
+        a.nprobe = nprobe; a.k = k; a.M = h->M; a.ksub = h->ksub; a.dsub = h->dsub; a.d = h->d;
+        a.nlist = h->nlist;
+        a.table_mode = h->by_residual ? 1 : 2;      // (use_precomputed_table is ignored: IndexIVFPQ.cpp:397-401)
+        a.max_codes = h->max_codes;
+        a.store_pairs = store_pairs;
+        StageTimer tm(h, 2);
+        if (!vlq::launch_scan_ip(a, h->stream)) return fail(VLQ_ERR_HIP, "internal: the inner-product scan is not built for this shape");
+        tm.stop();
+    }
+    HIP_TRY(hipGetLastError());
+    snprintf(h->last_scan, sizeof(h->last_scan), "scan_ip_kernel<%d>", vlq::ip_engineered(h->M, h->ksub) ? h->M / 4 : 0);
+    h->stat_nq += (uint64_t)n;
+    h->last_walk_first = -1; h->last_walk_limit = 0; h->last_walk_samples = 0; h->last_walk_counts = false;
+    h->last_placement = "none";
+    h->order_hist_ready = false;
+    return VLQ_OK;
+}
+
 int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev,
              const float* cdis_dev, int nprobe, int k, float* D_dev, int64_t* I_dev,
              int store_pairs) {
+    if (h->metric == 0) return scan_ip_dev(h, n, x_dev, keys_dev, cdis_dev, nprobe, k, D_dev, I_dev, store_pairs);
     if (h->polysemous_ht > 0) return scan_poly_dev(h, n, x_dev, keys_dev, cdis_dev, nprobe, k, D_dev, I_dev, store_pairs, nullptr);
     TRY(ensure_term2(h));
     const vlq::Env& env = vlq::env();
@@ -917,7 +1022,7 @@ void vlq_ivfpq_destroy(vlq_ivfpq_t h) {
                       &h->screen.half, &h->screen.mu, &h->screen.norm_c, &h->imi_screen[0].half, &h->imi_screen[0].mu,
                       &h->imi_screen[0].norm_c, &h->imi_screen[1].half, &h->imi_screen[1].mu, &h->imi_screen[1].norm_c,
                       &h->ws_qn_c, &h->ws_xh, &h->ws_xflags, &h->ws_screen_cnt,
-                      &h->rpq, &h->rcodes, &h->ws_sl, &h->ws_Dsl, &h->ws_r2, &h->ws_rcodes, &h->poly_stats, &h->ws_qcodes};
+                      &h->czero, &h->rpq, &h->rcodes, &h->ws_sl, &h->ws_Dsl, &h->ws_r2, &h->ws_rcodes, &h->poly_stats, &h->ws_qcodes};
     for (auto b : bufs) b->release();
     if (h->screen_cnt_host) (void)hipHostFree(h->screen_cnt_host);
     for (DevBuf* b : {&h->imi_ws2.xh, &h->imi_ws2.xflags, &h->imi_ws2.qn, &h->imi_ws2.qn_c, &h->imi_ws2.cand, &h->imi_ws2.tmin}) b->release();
@@ -1149,6 +1254,31 @@ int vlq_ivfpq_set_search_options(vlq_ivfpq_t h, int by_residual, int use_precomp
     return VLQ_OK;
 }
 
+int vlq_ivfpq_set_metric(vlq_ivfpq_t h, int metric) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
+    if (metric == h->metric) return VLQ_OK;
+    TRY(set_dev(h));
+    if (metric == 0) {
+        // term 2 is neither built nor kept under inner product: nlist * M * ksub floats for nothing
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->term2.release();
+        h->term2h.release();
+        h->term2_valid = false;
+        h->term2h_valid = false;
+    }
+    h->metric = metric;
+    // back to L2: what vlq_ivfpq_set_lists / vlq_ivfpq_add would have built by now
+    if (metric == 1 && h->have_coarse && h->have_pq && h->ntotal > 0) TRY(ensure_term2(h));
+    return VLQ_OK;
+}
+
+int vlq_ivfpq_get_metric(vlq_ivfpq_t h, int* metric) {
+    if (!h || !metric) return fail(VLQ_ERR_INVALID, "null argument");
+    *metric = h->metric;
+    return VLQ_OK;
+}
+
 int vlq_ivfpq_set_float16_tables(vlq_ivfpq_t h, int enable) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (enable && !(h->M == 16 && h->ksub == 256))
@@ -1172,7 +1302,7 @@ int vlq_ivfpq_coarse_screen_state(vlq_ivfpq_t h, int* enabled, uint64_t* rows, u
     if (h->coarse_screen && h->screen_cnt_host && h->screen_rows_copied >= 1024 &&
         (uint64_t)*h->screen_cnt_host * 200 > h->screen_rows_copied)
         h->coarse_screen = 0;
-    if (enabled) *enabled = (h->coarse_screen && (h->imi_nbits > 0 ? (h->imi_screen[0].ok && h->imi_screen[1].ok) : h->screen.ok)) ? 1 : 0;
+    if (enabled) *enabled = (h->metric != 0 && h->coarse_screen && (h->imi_nbits > 0 ? (h->imi_screen[0].ok && h->imi_screen[1].ok) : h->screen.ok)) ? 1 : 0;
     if (rows) *rows = h->screen_rows_seen;
     if (undecided) *undecided = h->screen_cnt_host ? *h->screen_cnt_host : 0u;
     return VLQ_OK;
@@ -1322,6 +1452,8 @@ int vlq_ivfpq_coarse_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe
 static int scan_runs_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const int64_t* kd, const float* cd, int nprobe, int k, float* Dd,
                          int64_t* Id, int store_pairs) {
     if (nprobe <= VLQ_MAX_NPROBE) return scan_dev(h, n, xd, kd, cd, nprobe, k, Dd, Id, store_pairs);
+    if (h->metric == 0)     // (the join of the runs is ascending)
+        return fail(VLQ_ERR_UNSUPPORTED, "inner-product metric with nprobe=%d > %d (runs of probes) is not built", nprobe, VLQ_MAX_NPROBE);
     if (h->polysemous_ht > 0)
         return fail(VLQ_ERR_UNSUPPORTED, "polysemous filtering with nprobe=%d > %d (runs of probes) is not built", nprobe, VLQ_MAX_NPROBE);
     if (h->max_codes != 0)
@@ -1414,7 +1546,7 @@ int vlq_ivfpq_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe, int k
     // (kernels.h OrderHist; the single-workgroup ordering of small batches does not use it)
     h->order_hist = vlq::OrderHist();
     h->order_hist_ready = false;
-    if (h->imi_nbits == 0 && n > 2048 && n <= 32768 && n <= query_page(h) && h->nlist <= (1 << 22)) {
+    if (h->metric != 0 && h->imi_nbits == 0 && n > 2048 && n <= 32768 && n <= query_page(h) && h->nlist <= (1 << 22)) {
         const size_t stride = vlq::query_order_bins_padded(h->nlist);
         TRY(h->ws_hist.reserve(2 * stride * sizeof(int)));
         HIP_TRY(hipMemsetAsync(h->ws_hist.p, 0, 2 * stride * sizeof(int), h->stream));
@@ -1457,6 +1589,7 @@ int vlq_ivfpq_query_tables(vlq_ivfpq_t h, int64_t n, const float* x, int inner_p
 int vlq_ivfpq_get_precomputed_table(vlq_ivfpq_t h, float* out) {
     TRY(check_ready(h, false));
     if (!out) return fail(VLQ_ERR_INVALID, "null out");
+    if (h->metric == 0) return fail(VLQ_ERR_STATE, "precomputed table not in use (inner-product metric: the table depends on the query only)");
     if (!(h->by_residual && h->use_precomputed_table == 1))
         return fail(VLQ_ERR_STATE, "precomputed table not in use");
     TRY(set_dev(h));
@@ -1693,6 +1826,7 @@ int vlq_ivfpq_reclaim_memory(vlq_ivfpq_t h, uint64_t* bytes_reclaimed) {
 // ---------------------------------------------------------------------------------------------------------------------
 static int refine_shape_ok(vlq_ivfpq_t h) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (h->metric == 0) return fail(VLQ_ERR_UNSUPPORTED, "IVFPQR with the inner-product metric is not built (the refine stage re-scores with fvec_L2sqr)");
     // a multi-index quantizer has no reconstruct (Index.cpp:64-67 throws): the reference cannot run IVFPQR on it either
     if (h->imi_nbits > 0) return fail(VLQ_ERR_UNSUPPORTED, "IVFPQR needs a flat coarse quantizer (a multi-index quantizer has no reconstruct)");
     if (!h->by_residual) return fail(VLQ_ERR_UNSUPPORTED, "IVFPQR needs by_residual (IndexIVFPQ.cpp:1297)");

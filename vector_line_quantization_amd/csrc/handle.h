@@ -93,6 +93,8 @@ struct AppendWs {   // lists.h AppendWorkspace (kept opaque here: handle.h is in
 struct vlq_ivfpq_s {
     int device = 0, d = 0, nlist = 0, M = 0, nbits = 0, ksub = 0, dsub = 0;
     int by_residual = 1, use_precomputed_table = 1;
+    int metric = 1;               // the reference's MetricType (Index.h): 0 = inner product, 1 = L2 (vlq_ivfpq_set_metric)
+    DevBuf czero;                 // [nlist] zeros: the centroid "norms" of the inner-product coarse stage
     int64_t max_codes = 0;
     int64_t ntotal = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;

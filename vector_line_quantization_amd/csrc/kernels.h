@@ -269,6 +269,36 @@ inline PolyLayout poly_layout(int M, int ksub, int nprobe, int k, int d) {
 }
 bool launch_scan_poly(const ScanArgs& a, const PolyArgs& p, hipStream_t s);
 
+// Inner-product metric (IndexIVFPQ with METRIC_INNER_PRODUCT, IndexIVFPQ.cpp:540-555, :609-624, :1039-1042; scan_ip.hip): one
+// workgroup per query keeps the negated per-query table in LDS for the whole walk and streams only codes.  a.table_mode 1 = by
+// residual (dis0 = -<q, centroid>, computed by the kernel: a.coarse_dis is not used), 2 = not by residual (dis0 = 0); a.queries,
+// a.coarse and a.pq_cent_t are read, a.term2 / a.qtab are not.  D comes out as inner products, descending, padded -FLT_MAX / -1.
+// Engineered for 8-bit codes of 4, 8, ..., 64 bytes; every other M / ksub <= 256 is read byte by byte.
+constexpr int kIpMaxProbes = 1024;
+inline bool ip_engineered(int M, int ksub) { return ksub == 256 && M >= 4 && M <= 64 && M % 4 == 0; }
+// the kernel's dynamic LDS, byte offsets: the table (later the merge area of the four waves' rows) at 0, the selections' queues,
+// the probe metadata, the query
+struct IpLayout { int selq, meta, sq; size_t bytes; };
+inline IpLayout ip_layout(int M, int ksub, int nprobe, int k, int d) {
+    IpLayout l;
+    const size_t table = (size_t)M * ksub * 4, merge = (size_t)4 * k * 8;
+    size_t o = ((table > merge ? table : merge) + 15) & ~(size_t)15;
+    l.selq = (int)o; o += 4 * 64 * 8;
+    l.meta = (int)o; o += (probe_meta_bytes(nprobe) + 7) & ~(size_t)7;
+    l.sq = (int)o; o += (size_t)d * 4;
+    l.bytes = o;
+    return l;
+}
+inline bool ip_shape_ok(int M, int ksub, int nprobe, int k, int d) {
+    return M >= 1 && ksub >= 2 && ksub <= 256 && nprobe >= 1 && nprobe <= kIpMaxProbes && k >= 1 && k <= 1024 &&
+           ip_layout(M, ksub, nprobe, k, d).bytes <= 160 * 1024;
+}
+bool launch_scan_ip(const ScanArgs& a, hipStream_t s);
+// coarse stage under the inner-product metric: the (distance, column) selections ran over the matrix of -2 <q, c> (the f32
+// MFMA distance kernel with zero norms), so cdis[i] = -0.5 * cdis[i] is the inner product, exactly; misses become -FLT_MAX
+// (the reference's min-heap starts there, Heap.h:62-64)
+void launch_coarse_ip_finish(float* cdis, const int64_t* keys, int64_t n, hipStream_t s);
+
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this
 inline size_t query_order_bins_padded(int nlist) {

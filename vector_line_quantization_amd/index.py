@@ -46,13 +46,19 @@ class GpuIVFPQ:
     (gpu/GpuIndexIVFPQ.h:41-234) / faiss::IndexIVFPQ (IndexIVFPQ.h:29-164) for the
     search path: construct, copy trained state in, search."""
 
-    def __init__(self, d, nlist, M, nbits, device=0):
+    METRICS = {"ip": 0, "l2": 1}      # the reference's MetricType (Index.h)
+
+    def __init__(self, d, nlist, M, nbits, device=0, metric="l2"):
         self.d, self.nlist, self.M, self.nbits = d, nlist, M, nbits
         self.ksub = 1 << nbits
         self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
         check(lib().vlq_ivfpq_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist),
                                      C.c_int(M), C.c_int(nbits)))
         self.device = device
+        if metric != "l2":
+            self.metric = metric
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -84,6 +90,20 @@ class GpuIVFPQ:
     def set_search_options(self, by_residual=True, use_precomputed_table=1, max_codes=0):
         check(lib().vlq_ivfpq_set_search_options(self._h, C.c_int(int(by_residual)),
                                                  C.c_int(use_precomputed_table), C.c_int64(max_codes)))
+
+    @property
+    def metric(self):
+        """"l2" (ascending squared distances) or "ip" (IndexIVFPQ with METRIC_INNER_PRODUCT: descending inner products,
+        -FLT_MAX / -1 padding; include/vlq_ivfpq.h says what is served)"""
+        m = C.c_int(1)
+        check(lib().vlq_ivfpq_get_metric(self._h, C.byref(m)))
+        return "ip" if m.value == 0 else "l2"
+
+    @metric.setter
+    def metric(self, metric):
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        check(lib().vlq_ivfpq_set_metric(self._h, C.c_int(self.METRICS[metric])))
 
     def set_float16_tables(self, enable=True):
         """GpuIndexIVFPQConfig::useFloat16LookupTables for the plain IVFPQ search (include/vlq_ivfpq.h)"""

@@ -22,10 +22,31 @@ def shard_bounds(n, world, rank):
     return lo, hi, per
 
 
-def sharded_search(local_search, x, nprobe, k, group=None, D_out=None, I_out=None):
+def _metric_of(local_search, metric):
+    """The metric the rows of `local_search` are ordered by: the caller's word, else the `metric` of the index whose bound
+    method `local_search` is (GpuIVFPQ.search), else "l2" (a plain function tells nothing: pass metric="ip" for one that
+    searches under inner product, or the padding / the merge below are those of L2)."""
+    if metric is None:
+        metric = getattr(getattr(local_search, "__self__", None), "metric", None)
+        if metric is None:
+            metric = "l2"
+    if metric not in ("l2", "ip"):
+        raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+    return metric
+
+
+def pad_distance(metric):
+    """What an empty result slot holds: FLT_MAX under "l2" (rows ascend), -FLT_MAX under "ip" (rows descend)."""
+    import torch
+    return torch.finfo(torch.float32).max if metric == "l2" else -torch.finfo(torch.float32).max
+
+
+def sharded_search(local_search, x, nprobe, k, group=None, D_out=None, I_out=None, metric=None):
     """x: the FULL query batch [n, d] (torch tensor, same on every rank).
     local_search(xs, nprobe, k) -> (D[ns,k] float32, I[ns,k] int64) torch tensors on
-    x's device.  Returns the full (D[n,k], I[n,k]) on every rank."""
+    x's device.  Returns the full (D[n,k], I[n,k]) on every rank.  metric: the metric every rank's handle was given
+    (set_metric below); it only decides what an unused slot of the gather holds (-FLT_MAX under "ip").  None: read from the
+    index `local_search` is a bound method of (_metric_of)."""
     import torch
     import torch.distributed as dist
 
@@ -33,10 +54,12 @@ def sharded_search(local_search, x, nprobe, k, group=None, D_out=None, I_out=Non
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     n = x.shape[0]
     lo, hi, per = shard_bounds(n, world, rank)
+    metric = _metric_of(local_search, metric)
     if world == 1:
         return local_search(x, nprobe, k)
     # equal-sized slots so that one all_gather_into_tensor moves everything
-    Dl = torch.full((per, k), torch.finfo(torch.float32).max, dtype=torch.float32, device=x.device)
+    pad = pad_distance(metric)
+    Dl = torch.full((per, k), pad, dtype=torch.float32, device=x.device)
     Il = torch.full((per, k), -1, dtype=torch.int64, device=x.device)
     if hi > lo:
         d, i = local_search(x[lo:hi], nprobe, k)
@@ -51,12 +74,18 @@ def sharded_search(local_search, x, nprobe, k, group=None, D_out=None, I_out=Non
     return D, I
 
 
-def list_sharded_search(local_search, x, nprobe, k, group=None):
+def list_sharded_search(local_search, x, nprobe, k, group=None, metric=None):
     """The reference's MPI mode (gpu/GpuIndexIVFPQ.cu:2106-2242, gpu/test/deep1b16_query.cpp:
     193-428) for indexes too large to replicate: every rank holds the inverted lists of a
     contiguous list range (all other lists empty), runs the FULL coarse stage for ALL queries
     (identical on every rank), scans only the probed lists it owns, then the per-rank top-k
-    are all-gathered and merged (a select, never a sum).  x: full batch, same on every rank."""
+    are all-gathered and merged (a select, never a sum).  x: full batch, same on every rank.
+    L2 only: the merge keeps the k SMALLEST values; rows of descending inner products need a descending merge.  The metric is
+    the caller's word or read from the index `local_search` is a bound method of (_metric_of); a plain function that searches
+    under inner product MUST come with metric="ip", or its rows are merged ascending."""
+    if _metric_of(local_search, metric) != "l2":
+        raise NotImplementedError("list-range sharding under the inner-product metric is not built: the merge of the per-rank "
+                                  "rows is ascending (use sharded_search: the index replicated, the queries split)")
     import torch
     import torch.distributed as dist
 
@@ -107,3 +136,9 @@ def set_polysemous_ht(index, ht):
     handle.  Replica or list range alike, the filter acts per stored code, so shards filter exactly as one index would; each
     rank searches only its own handle, so no collective is needed."""
     index.set_polysemous_ht(ht)
+
+
+def set_metric(index, metric):
+    """The metric ("l2" or "ip") for a query-sharded search: every rank calls this with the same value and sets it on its own
+    handle; pass the same value to sharded_search.  Each rank searches only its own handle, so no collective is needed."""
+    index.metric = metric
