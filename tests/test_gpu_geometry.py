@@ -237,7 +237,7 @@ def deep1b_own():
     """BASELINE configs[3] (tests/deep1b_imi_pq.cpp shape with the flat 2^17-list quantizer the config names):
     d = 96 (dsub = 6), nlist = 131 072, M = 16 x 8 bit, nprobe = 128.  The 2 GiB term2 table
     ((size_t)key * E addressing), the 131 072-column coarse select from tile minima and the 16 384-row
-    distance-matrix pages (api.hip query_page) all run at full size; the database is 400 000
+    distance-matrix pages (coarse_stage.hip query_page) all run at full size; the database is 400 000
     device-encoded vectors placed on the lists the checked queries probe (300 000 through encode +
     set_lists, 100 000 appended on the device on top of them)."""
     from oracle.pyoracle import OracleIndex

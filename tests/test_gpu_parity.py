@@ -162,7 +162,7 @@ def test_wide_rows_two_level_select(nlist, d, nprobe):
 
 
 # 1250 / 2500: a 10 000-query batch over 8 / 4 GPUs; 1025 ... 1500, 2100: batches whose last round of workgroups is thin -- its
-# queries are split into parts (api.hip: tail_r / tail_p), the whole queries in front of them are not
+# queries are split into parts (scan_stage.hip: tail_r / tail_p), the whole queries in front of them are not
 @pytest.mark.parametrize("nq", [1, 3, 16, 100, 500, 1025, 1031, 1100, 1250, 1500, 2100, 2500, 3000])
 def test_small_batches_split_scan(nq):
     """Serving-size batches: a query's probes are split over up to 8 workgroups and the partial rows

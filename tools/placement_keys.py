@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 
 def spatial_list_rank(cent):
-    """numpy restatement of spatial_list_rank (csrc/api.hip): recursive two-means bisection of the centroids"""
+    """numpy restatement of spatial_list_rank (csrc/coarse_stage.hip): recursive two-means bisection of the centroids"""
     nlist = cent.shape[0]
     order = np.arange(nlist)
     stack = [(0, nlist)]

@@ -1,6 +1,7 @@
-// Internal: the index handle and small host helpers shared by api.hip and line_api.hip.
+// Internal: the index handle and small host helpers shared by the host files (api.hip, the stage files, line_api.hip).
 #pragma once
 #include "../../include/vlq_ivfpq.h"
+#include "dev_buf.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -41,27 +42,14 @@ inline int fail(int code, const char* fmt, ...) {
         if (rc_ != VLQ_OK) return rc_; \
     } while (0)
 
-// growable device buffer
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return VLQ_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            e = hipMalloc(&p, bytes);
-            want = bytes;
-        }
-        if (e != hipSuccess) { p = nullptr; return fail(VLQ_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
-        cap = want;
-        return VLQ_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+// growable device buffer (dev_buf.h) over hipMalloc / hipFree
+struct HipAlloc {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+    static void forget(int) { (void)hipGetLastError(); }
+    static int failed(size_t bytes, int e) { return fail(VLQ_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString((hipError_t)e)); }
 };
+typedef BasicDevBuf<HipAlloc> DevBuf;
 
 // 0 = ordinary (pageable) host memory, 1 = device / managed memory, 2 = page-locked host memory that kernels can
 // address (hipHostMalloc / hipHostRegister: what GpuResources::getPinnedMemory hands out); *dev = its device-side address
@@ -178,7 +166,6 @@ struct vlq_ivfpq_s {
     bool prof = false, prof_scan_only = false;
     int prof_every = 1;              // scan-only timing of every prof_every-th search call (profile mode 3: every 4th)
     uint64_t prof_seq = 0;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     struct Pending { hipEvent_t a, b; int stage; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> ev_pool;
@@ -187,18 +174,49 @@ struct vlq_ivfpq_s {
 };
 
 
-// internal entry points implemented in api.hip
+// internal entry points: what crosses the host files
+namespace vlq { struct ListStore; }   // lists.h
 namespace vlq_detail {
+// api.hip: staging and the checks the entry points share
 int set_dev(vlq_ivfpq_t h);
 int stage_in(vlq_ivfpq_t h, const void* src, size_t bytes, DevBuf& ws, const void** out);
-int stage_out(void* dst, size_t bytes, DevBuf& ws, void** dev, bool* need_copy, bool* zero_copy = nullptr);
-int finish_outputs(vlq_ivfpq_t h, bool copyD, void* D, const void* Dd, size_t bytesD, bool copyI,
-                   void* I, const void* Id, size_t bytesI);
+// The rows of a call's two outputs (D and I; the coarse stage's distances and keys).  stage() picks where the kernels write each:
+// the caller's device memory, with zero_copy_ok its page-locked host memory, or the workspace; finish() copies workspace rows back
+// and synchronises (rows written straight into page-locked memory: synchronises too).
+struct StagedRows {
+    void *D = nullptr, *I = nullptr, *hostD = nullptr, *hostI = nullptr;      // device-side destinations, the caller's
+    size_t bytesD = 0, bytesI = 0;
+    bool copyD = false, copyI = false, zero_copy = false;
+    int stage(void* D_out, size_t bytes_D, DevBuf& ws_D, void* I_out, size_t bytes_I, DevBuf& ws_I, bool zero_copy_ok = false);
+    int finish(vlq_ivfpq_t h);
+    bool synchronous() const { return copyD || copyI; }    // host outputs: finish() has synchronised (read_bad_key may follow)
+};
+int check_ready(vlq_ivfpq_t h, bool need_lists);
+int check_search_args(vlq_ivfpq_t h, int64_t n, const void* x, int nprobe, int k, const void* D, const void* I);
+int read_bad_key(vlq_ivfpq_t h);
+vlq::ListStore list_store(vlq_ivfpq_t h);
+// scan_stage.hip
+struct StageTimer {      // books the stream time between its construction and stop() to a stage (vlq_ivfpq_profile)
+    vlq_ivfpq_t h; int stage; hipEvent_t a = nullptr, b = nullptr;
+    StageTimer(vlq_ivfpq_t h_, int stage_);
+    void stop();
+};
+void drain_profile(vlq_ivfpq_t h);
 int ensure_term2(vlq_ivfpq_t h);
+int scan_poly_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev, const float* cdis_dev, int nprobe, int k,
+                  float* D_dev, int64_t* I_dev, int store_pairs, uint8_t* qcodes);
+int scan_runs_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const int64_t* kd, const float* cd, int nprobe, int k, float* Dd,
+                  int64_t* Id, int store_pairs);
+// coarse_stage.hip
 int64_t query_page(vlq_ivfpq_t h);
 // coarse stage of ONE page (n <= query_page); keep_matrix: the [n][nlist] distance matrix must be
 // left in h->ws_dist (the VLQ line select reads it) -- a 1-NN assignment otherwise never writes it;
 // zero_qnorm drops |q|^2 (the VLQ path, impl/Distance.cu:286-291)
 int coarse_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev,
                 int64_t* keys_dev, bool zero_qnorm, bool direct, bool keep_matrix = false);
+int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev, int64_t* keys_dev);
+int ip_unsupported(vlq_ivfpq_t h);
+void screen_defeated(vlq_ivfpq_t h);
+void spatial_list_rank(const float* cent, int nlist, int d, std::vector<int>& rank);
+int build_screen(vlq_ivfpq_t h, const float* hc, const float* cent_dev, int n, int d, vlq_ivfpq_s::ScreenSet& sc);
 }  // namespace vlq_detail

@@ -160,17 +160,12 @@ int vlq_line_create(vlq_line_t* out, int device, int d, int nlist, int M, int nb
 
 void vlq_line_destroy(vlq_line_t h) {
     if (!h) return;
-    if (h->base) { (void)hipSetDevice(h->base->device); (void)hipStreamSynchronize(h->base->stream); }
-    DevBuf* bufs[] = {&h->edge_info, &h->edge_dist, &h->lambda_info, &h->codes, &h->lambdas, &h->ids,
-                      &h->line_off, &h->line_len, &h->ws_append.cnt, &h->ws_append.cstart, &h->ws_append.keys_in,
-                      &h->ws_append.keys_out, &h->ws_append.sort_tmp, &h->ws_near, &h->ws_line, &h->ws_lamf, &h->ws_lamb, &h->ws_res,
-                      &h->ws_codes, &h->ws_sel_line, &h->ws_sel_b2, &h->ws_sel_g, &h->ws_sel_meta, &h->ws_sel_cnt, &h->ws_x, &h->ws_D,
-                      &h->ws_I, &h->ws_keys, &h->ws_cdis, &h->stats, &h->term2h, &h->ws_qtabh, &h->pconst, &h->pconsth, &h->ws_part_keys};
-    for (auto b : bufs) b->release();
+    const vlq_ivfpq_t base = h->base;
+    if (base) { (void)hipSetDevice(base->device); (void)hipStreamSynchronize(base->stream); }
     for (auto& p : h->prof_pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto e : h->prof_pool) (void)hipEventDestroy(e);
-    if (h->base) vlq_ivfpq_destroy(h->base);
-    delete h;
+    delete h;       // the line index's DevBufs free their blocks here: before the embedded handle destroys the stream
+    if (base) vlq_ivfpq_destroy(base);
 }
 
 int vlq_line_set_stream(vlq_line_t h, void* s) {
@@ -451,10 +446,8 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
     const size_t E = (size_t)b->M * b->ksub;
     const void* xd;
     TRY(stage_in(b, x, (size_t)n * b->d * 4, h->ws_x, &xd));
-    void *Dd, *Id;
-    bool copyD, copyI;
-    TRY(stage_out(D, (size_t)n * k * 4, h->ws_D, &Dd, &copyD));
-    TRY(stage_out(I, (size_t)n * k * 8, h->ws_I, &Id, &copyI));
+    StagedRows out;
+    TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I));
     const int64_t page = query_page(b);
     const int64_t pn = std::min(n, page);
     TRY(h->ws_keys.reserve((size_t)pn * nprobe * 8));
@@ -521,7 +514,7 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
         a.sel_line = sel_line; a.sel_b2 = h->ws_sel_b2.as<float>(); a.sel_g = h->ws_sel_g.as<float>();
         if (fp16) { a.term2h = h->term2h.as<uint16_t>(); a.qtabh = h->ws_qtabh.as<uint16_t>(); }
         a.sel_meta = with_meta ? h->ws_sel_meta.as<vlq::LineMeta>() : nullptr; a.sel_cnt = h->ws_sel_cnt.as<int32_t>();
-        a.D = (float*)Dd + i0 * k; a.I = (int64_t*)Id + i0 * k;
+        a.D = (float*)out.D + i0 * k; a.I = (int64_t*)out.I + i0 * k;
         a.ncode = h->stats.as<unsigned long long>();
         a.nq = ni; a.w1 = w1; a.k = k; a.M = b->M; a.ksub = b->ksub; a.nedge = h->nedge;
         a.max_line_codes = VLQ_LINE_MAX_CODES;
@@ -553,7 +546,7 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
         HIP_TRY(hipGetLastError());
     }
     if (lines_out) HIP_TRY(hipMemcpyAsync(lines_out, h->ws_sel_line.p, (size_t)n * w1 * 4, hipMemcpyDeviceToHost, b->stream));
-    TRY(finish_outputs(b, copyD, D, Dd, (size_t)n * k * 4, copyI, I, Id, (size_t)n * k * 8));
+    TRY(out.finish(b));
     if (lines_out) HIP_TRY(hipStreamSynchronize(b->stream));
     return VLQ_OK;
 }

@@ -26,7 +26,6 @@ struct ListStore {
 };
 
 typedef AppendWs AppendWorkspace;   // handle.h
-inline void release(AppendWorkspace& w) { w.cnt.release(); w.cstart.release(); w.keys_in.release(); w.keys_out.release(); w.sort_tmp.release(); }
 
 // Append n encoded vectors: vector i goes to the end of list assign[i] (assign[i] < 0: dropped,
 // IndexIVFPQ.cpp:238-243), vectors of one list keep their input order (:236-248).  All

@@ -141,14 +141,14 @@ int lists_sync_host(ListStore& ls, hipStream_t s) {
 }
 
 // move every list to noff[i] (device array [nlist+1], capacities noff[i+1] - noff[i] >= len[i],
-// noff[nlist] = cap); takes ownership of noff; synchronises
+// noff[nlist] = cap); noff comes back holding the old starts; synchronises
 static int relayout_dev(ListStore& ls, DevBuf& noff, int64_t cap, hipStream_t s) {
     const int64_t nlist = ls.nlist;
     DevBuf nc, nl, ni;
     int rc = nc.reserve((size_t)cap * ls.code_size + 16);
     if (rc == VLQ_OK) rc = ni.reserve((size_t)cap * 8 + 16);
     if (rc == VLQ_OK && ls.lambdas) rc = nl.reserve((size_t)cap * ls.side_size + 16);
-    if (rc != VLQ_OK) { nc.release(); nl.release(); ni.release(); noff.release(); return rc; }
+    if (rc != VLQ_OK) return rc;
     hipError_t e = hipSuccess;
     if (ls.codes->p) {
         const unsigned g = (unsigned)((nlist + 255) / 256);
@@ -160,16 +160,12 @@ static int relayout_dev(ListStore& ls, DevBuf& noff, int64_t cap, hipStream_t s)
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // the old buffers die below
-    if (e != hipSuccess) {
-        nc.release(); nl.release(); ni.release(); noff.release();
-        return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e));
     std::swap(*ls.codes, nc);
     std::swap(*ls.ids, ni);
     if (ls.lambdas) std::swap(*ls.lambdas, nl);
     std::swap(*ls.off, noff);
-    nc.release(); nl.release(); ni.release(); noff.release();
-    return VLQ_OK;
+    return VLQ_OK;      // (the old blocks go with nc / nl / ni here, the old starts with the caller's noff)
 }
 
 // same, from a host array (reserve / reclaim); the host copies must be current
@@ -179,7 +175,7 @@ int lists_relayout(ListStore& ls, std::vector<int64_t>& new_off, hipStream_t s) 
     TRY(noff.reserve(((size_t)nlist + 1) * 8));
     hipError_t e = hipMemcpyAsync(noff.p, new_off.data(), ((size_t)nlist + 1) * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { noff.release(); return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e));
     TRY(relayout_dev(ls, noff, new_off[(size_t)nlist], s));
     ls.h_off->swap(new_off);
     return VLQ_OK;
@@ -268,7 +264,7 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
         DevBuf caps, noff;
         int rc = caps.reserve(((size_t)nlist + 1) * 8);
         if (rc == VLQ_OK) rc = noff.reserve(((size_t)nlist + 1) * 8);
-        if (rc != VLQ_OK) { caps.release(); noff.release(); return rc; }
+        if (rc != VLQ_OK) return rc;
         hipLaunchKernelGGL(grow_caps_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), ls.len->as<int64_t>(),
                            ls.off->as<int64_t>(), nlist, caps.as<int64_t>());
         size_t b2 = 0;
@@ -281,8 +277,8 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
         int64_t cap = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&cap, noff.as<int64_t>() + nlist, 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        caps.release();
-        if (e != hipSuccess) { noff.release(); return fail(VLQ_ERR_HIP, "list growth failed: %s", hipGetErrorString(e)); }
+        caps.release();      // (not held across the relayout's allocations)
+        if (e != hipSuccess) return fail(VLQ_ERR_HIP, "list growth failed: %s", hipGetErrorString(e));
         TRY(relayout_dev(ls, noff, cap, s));
         if (relaid) *relaid = true;
     }
