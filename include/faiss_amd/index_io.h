@@ -3,6 +3,7 @@
 // quantizer, per-list id and code vectors.
 //   "IxFI"  IndexFlatIP
 //   "IxF2"  IndexFlatL2            "Imiq"  MultiIndexQuantizer        "IvPQ"  IndexIVFPQ
+//   "IvFl"  IndexIVFFlat (index_io.cpp:276-283, :597-603)
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
 // and rejected.
@@ -84,6 +85,16 @@ inline void write_index(const Index* idx, FILE* f) {
     w1(f, fourcc("Imiq"));
     write_header(idx, f);
     write_pq(miq->pq, f);
+  } else if (const IndexIVFFlat* ivfl = dynamic_cast<const IndexIVFFlat*>(idx)) {
+    w1(f, fourcc("IvFl"));                     // index_io.cpp:276-283
+    write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
+    w1(f, ivfl->nlist);
+    w1(f, ivfl->nprobe);
+    write_index(ivfl->quantizer, f);
+    for (size_t i = 0; i < ivfl->nlist; i++) wvec(f, ivfl->ids[i]);
+    w1(f, ivfl->maintain_direct_map);
+    wvec(f, ivfl->direct_map);
+    for (size_t i = 0; i < ivfl->nlist; i++) wvec(f, ivfl->vecs[i]);
   } else if (const IndexIVFPQ* ivpq = dynamic_cast<const IndexIVFPQ*>(idx)) {
     w1(f, fourcc("IvPQ"));
     write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
@@ -133,6 +144,25 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     read_header(miq.get(), f);
     read_pq(miq->pq, f);
     return miq.release();
+  }
+  if (h == fourcc("IvFl")) {                   // index_io.cpp:597-603
+    std::unique_ptr<IndexIVFFlat> iv(new IndexIVFFlat());
+    read_header(iv.get(), f);                  // read_ivf_header, index_io.cpp:459-473
+    r1(f, iv->nlist);
+    r1(f, iv->nprobe);
+    iv->quantizer = read_index(f, precompute);
+    iv->own_fields = true;
+    iv->ids.resize(iv->nlist);
+    for (size_t i = 0; i < iv->nlist; i++) rvec(f, iv->ids[i]);
+    r1(f, iv->maintain_direct_map);
+    rvec(f, iv->direct_map);
+    iv->vecs.resize(iv->nlist);
+    for (size_t i = 0; i < iv->nlist; i++) {
+      rvec(f, iv->vecs[i]);
+      FAISS_THROW_IF_NOT(iv->vecs[i].size() == iv->ids[i].size() * (size_t)iv->d);
+    }
+    iv->lists_changed();
+    return iv.release();
   }
   if (h == fourcc("IvPQ")) {
     // a minimal quantizer to construct with; replaced by the stored one

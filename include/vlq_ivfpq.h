@@ -326,6 +326,64 @@ int vlq_ivfpq_reset_walk_state(vlq_ivfpq_t h);
 int vlq_ivfpq_profile(vlq_ivfpq_t h, int enable);
 int vlq_ivfpq_profile_read(vlq_ivfpq_t h, double ms[3], int64_t* calls, int reset);
 
+/* ---- IVFFlat: inverted lists of the vectors themselves, exact distances (faiss::IndexIVFFlat, IndexIVF.h:132-205,
+ * IndexIVF.cpp:200-400; gpu/GpuIndexIVFFlat.h; what index_factory builds for "IVFx,Flat").  A handle of its own: the coarse
+ * quantizer is the flat one of the IVFPQ handle (same kernels, same keys and distances bit for bit: IndexFlatL2 for L2,
+ * IndexFlatIP for inner product), the lists hold rows of d floats, list-contiguous, and the scan (csrc/scan_flat.hip)
+ * computes fvec_L2sqr / fvec_inner_product in the reference's operation order (utils.cpp:481-533), so D is bit-identical
+ * to search_knn_L2sqr / search_knn_inner_product (IndexIVF.cpp:272-370).
+ *   L2 (metric 1):            rows ascending, a missing result is FLT_MAX / -1   (max-heap, dis < top, :357-361)
+ *   inner product (metric 0): rows descending, a missing result is -FLT_MAX / -1 (min-heap, ip > top, :307-311)
+ * An equal value never replaces an earlier one of the scan order.  Keys < 0 are skipped (:292-295, :342-345); a key >= nlist
+ * aborts the reference's search (:296-300, :346-350): reported as for vlq_ivfpq_search_preassigned (VLQ_ERR_INVALID from the
+ * call with a host D or I, from the next vlq_ivfflat_stats() otherwise).
+ * Limits: k <= VLQ_MAX_K, nprobe <= VLQ_MAX_NPROBE, 4 * d + 24 * nprobe within the kernel's LDS (d up to about 29 000):
+ * VLQ_ERR_UNSUPPORTED otherwise, there is no other path.  float16 storage (GpuIndexIVFFlatConfig::useFloat16IVFStorage),
+ * range_search, update_vectors and the direct map are not built.
+ * Pointers marked [h|d] as above. */
+typedef struct vlq_ivfflat_s* vlq_ivfflat_t;
+
+/* IndexIVFFlat::IndexIVFFlat (IndexIVF.cpp:204-209).  metric: MetricType of Index.h (0 = inner product, 1 = L2). */
+int vlq_ivfflat_create(vlq_ivfflat_t* out, int device, int d, int nlist, int metric);
+void vlq_ivfflat_destroy(vlq_ivfflat_t h);
+/* as vlq_ivfpq_set_stream */
+int vlq_ivfflat_set_stream(vlq_ivfflat_t h, void* hip_stream);
+/* the trained quantizer: centroids[nlist*d] [h|d] (IndexIVF::train leaves them in quantizer, IndexIVF.cpp:80-118) */
+int vlq_ivfflat_set_coarse_centroids(vlq_ivfflat_t h, const float* centroids);
+/* IndexIVFFlat::vecs / IndexIVF::ids (IndexIVF.h:55, :135), list-contiguous: vecs[ntotal*d], ids[ntotal],
+ * list_offsets[nlist+1] [h|d].  Replaces the lists. */
+int vlq_ivfflat_set_lists(vlq_ivfflat_t h, const float* vecs, const int64_t* ids, const int64_t* list_offsets);
+/* IndexIVFFlat::add_with_ids (IndexIVF.cpp:216-219): quantizer->assign (1-NN), then add_core; assigned and appended on the
+ * device.  x[n*d] [h|d], xids[n] [h|d] or NULL. */
+int vlq_ivfflat_add(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* xids);
+/* IndexIVFFlat::add_core with precomputed_idx (IndexIVF.cpp:221-262): vector i goes to the end of list assign[i]; a negative
+ * list id drops it (:243-244); vectors of one list keep their input order; the id of vector i is xids ? xids[i] :
+ * ntotal + i (:241) and ntotal grows by the vectors kept (:261).  assign[n] [h|d]; an id >= nlist (an assert of the
+ * reference, :245) drops the vector too. */
+int vlq_ivfflat_add_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* xids, const int64_t* assign);
+/* GpuIndexIVFFlat::reserveMemory / reclaimMemory (gpu/GpuIndexIVFFlat.h:56-63), as for the IVFPQ handle */
+int vlq_ivfflat_reserve_memory(vlq_ivfflat_t h, int64_t num_vecs);
+int vlq_ivfflat_reclaim_memory(vlq_ivfflat_t h, uint64_t* bytes_reclaimed);
+int64_t vlq_ivfflat_ntotal(vlq_ivfflat_t h);
+/* IndexIVF::get_list_size (IndexIVF.h:91-92); vecs_out[len*d], ids_out[len] host buffers (either may be NULL) */
+int vlq_ivfflat_list_length(vlq_ivfflat_t h, int list_id, int64_t* len);
+int vlq_ivfflat_get_list(vlq_ivfflat_t h, int list_id, float* vecs_out, int64_t* ids_out);
+/* IndexIVFFlat::reset (IndexIVF.cpp:533-539, :93-100): every list emptied, ntotal = 0; the quantizer stays */
+int vlq_ivfflat_reset(vlq_ivfflat_t h);
+/* quantizer->search(n, x, nprobe) (what quantizer->assign calls, Index.cpp:31-38): cdis / keys [n*nprobe] [h|d] */
+int vlq_ivfflat_coarse_search(vlq_ivfflat_t h, int64_t n, const float* x, int nprobe, float* cdis, int64_t* keys);
+/* IndexIVFFlat::search (IndexIVF.cpp:373-380): quantizer->assign with nprobe, then search_preassigned.  x, D, I [h|d]. */
+int vlq_ivfflat_search(vlq_ivfflat_t h, int64_t n, const float* x, int nprobe, int k, float* D, int64_t* I);
+/* IndexIVFFlat::search_preassigned (IndexIVF.cpp:383-398): keys[n*nprobe] [h|d] */
+int vlq_ivfflat_search_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, int k,
+                                   float* D, int64_t* I);
+/* IndexIVFFlatStats (IndexIVF.h:111-119; IndexIVF.cpp:317-319, :367-369) since the last reset: queries, lists visited (empty
+ * ones included), distances computed.  Synchronises the stream; raises a pending bad-key error. */
+int vlq_ivfflat_stats(vlq_ivfflat_t h, uint64_t* nq, uint64_t* nlist_visited, uint64_t* ndis, int reset);
+/* Introspection, speed only: the kernel instantiation and read path of the last scan, as text:
+ *   "kernel=scan_flat_kernel<1, L2> read=tile128 lds=40304".  Synchronises the stream. */
+int vlq_ivfflat_last_scan_info(vlq_ivfflat_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

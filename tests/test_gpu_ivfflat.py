@@ -1,0 +1,229 @@
+"""GPU: IVFFlat (vlq.GpuIVFFlat, csrc/scan_flat.hip) against fixtures made from the reference's own IndexFlatL2 / IndexFlatIP +
+IndexIVFFlat (tests/golden/make_golden_ivfflat.py).  Fixtures only: no reference tree, no oracle."""
+import os
+
+import numpy as np
+import pytest
+
+import vector_line_quantization_amd as vlq
+from util import GOLDEN, assert_same_topk, bits
+
+pytestmark = pytest.mark.gpu
+ERR_INVALID, ERR_UNSUPPORTED = 1, 3
+CASES = ["flat_l2_d32", "flat_ip_d32", "flat_l2_d128_long", "flat_tail_d30_l2", "flat_tail_d30_ip", "flat_tail_d5_l2",
+         "flat_tail_d5_ip", "flat_tail_d3_l2", "flat_tail_d3_ip", "flat_padding_ties_l2", "flat_padding_ties_ip", "flat_kwide"]
+METRIC = {0: "ip", 1: "l2"}
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+PAD_BITS = {"l2": FLT_MAX.view(np.uint32), "ip": np.float32(-FLT_MAX).view(np.uint32)}
+
+
+def load(name):
+    z = np.load(os.path.join(GOLDEN, "ivfflat", name + ".npz"))
+    return {k: z[k] for k in z.files}
+
+
+def make_index(z, lists=True):
+    g = vlq.GpuIVFFlat(int(z["d"]), int(z["nlist"]), device=0, metric=METRIC[int(z["metric"])])
+    g.set_coarse_centroids(z["coarse_centroids"])
+    if lists:
+        g.set_lists(z["vecs"], z["ids"], z["list_offsets"])
+    return g
+
+
+@pytest.fixture(scope="module", params=CASES)
+def setup(request):
+    z = load(request.param)
+    g = make_index(z)
+    yield request.param, z, g
+    g.close()
+
+
+def test_seam(setup):
+    """search_preassigned against the reference's: D as bits, labels exact (free only inside a tie group across the k-th
+    place, which only the duplicate fixtures have), the padding per metric, IndexIVFFlatStats, the kernel that ran"""
+    name, z, g = setup
+    k, metric = int(z["k"]), METRIC[int(z["metric"])]
+    assert g.ntotal == z["ids"].shape[0]
+    g.stats(reset=True)
+    D, I = g.search_preassigned(z["xq"], z["keys"], k)
+    nq, nlistv, ndis = g.stats(reset=True)
+    loose = assert_same_topk(D, I, z["D"], z["I"], name)
+    assert loose == 0 or "ties" in name
+    if "ties" in name:
+        assert loose < D.shape[0] * 2 // 3 + 1
+    assert (bits(D)[I == -1] == PAD_BITS[metric]).all()
+    assert (nq, nlistv, ndis) == (z["xq"].shape[0], int(z["nlistv"].sum()), int(z["ndis"].sum()))
+    info = g.last_scan_info()
+    kpl = 1 if k <= 64 else 4 if k <= 256 else 16
+    assert "kernel=scan_flat_kernel<%d, %s>" % (kpl, metric.upper()) in info
+    assert ("read=tile128" if int(z["d"]) % 4 == 0 else "read=dword") in info
+
+
+def test_extra_k_on_the_same_data():
+    z = load("flat_kwide")
+    g = make_index(z)
+    D, I = g.search_preassigned(z["xq"], z["keys"], 1)
+    assert assert_same_topk(D, I, z["D_k1"], z["I_k1"], "k = 1") == 0
+    assert "scan_flat_kernel<1, L2>" in g.last_scan_info()
+    # a k between the two: the first rows of the k = 1024 answer (no ties in this fixture), through the KPL = 4 instantiation
+    D, I = g.search_preassigned(z["xq"], z["keys"], 200)
+    assert np.array_equal(bits(D), bits(z["D"][:, :200])) and np.array_equal(I, z["I"][:, :200])
+    assert "scan_flat_kernel<4, L2>" in g.last_scan_info()
+    g.close()
+
+
+def test_stats_per_query():
+    z = load("flat_padding_ties_l2")
+    g = make_index(z)
+    for i in range(0, z["xq"].shape[0], 5):
+        g.stats(reset=True)
+        g.search_preassigned(z["xq"][i:i + 1], z["keys"][i:i + 1], int(z["k"]))
+        assert g.stats(reset=True) == (1, int(z["nlistv"][i]), int(z["ndis"][i]))
+    g.close()
+
+
+@pytest.mark.parametrize("name", ["flat_l2_d32", "flat_ip_d32", "flat_tail_d30_l2", "flat_l2_d128_long"])
+def test_search_is_coarse_then_preassigned(name):
+    z = load(name)
+    g = make_index(z)
+    nprobe, k = int(z["nprobe"]), int(z["k"])
+    cdis, keys = g.coarse_search(z["xq"], nprobe)
+    D0, I0 = g.search_preassigned(z["xq"], keys, k)
+    D, I = g.search(z["xq"], nprobe, k)
+    assert np.array_equal(bits(D), bits(D0)) and np.array_equal(I, I0)
+    # one query at a time (the coarse stage's small-batch path) finds what the reference's quantizer->assign found
+    D1, I1 = g.search(z["xq"][:3], nprobe, k)
+    c1, k1 = g.coarse_search(z["xq"][:3], nprobe)
+    Dp, Ip = g.search_preassigned(z["xq"][:3], k1, k)
+    assert np.array_equal(bits(D1), bits(Dp)) and np.array_equal(I1, Ip)
+    g.close()
+
+
+@pytest.mark.parametrize("metric", ["l2", "ip"])
+def test_whole_search_against_the_reference(metric):
+    """integer-valued data: every distance is exact, so the keys do not depend on how the coarse stage sums"""
+    z = load("flat_coarse_int")
+    p = metric + "_"
+    zz = {nm[len(p):]: v for nm, v in z.items() if nm.startswith(p)}
+    nprobe, k, ns = int(z["nprobe"]), int(z["k"]), int(z["n_small"])
+    g = vlq.GpuIVFFlat(int(z["d"]), int(z["nlist"]), metric=metric)
+    g.set_coarse_centroids(zz["coarse_centroids"])
+    g.set_lists(zz["vecs"], zz["ids"], zz["list_offsets"])
+    _c, keys = g.coarse_search(zz["xq"], nprobe)
+    assert np.array_equal(keys, zz["keys"])
+    D, I = g.search(zz["xq"], nprobe, k)                 # 24 queries: the matrix path of the coarse stage
+    assert assert_same_topk(D, I, zz["Ds"], zz["Is"], metric + " batch") == 0
+    D, I = g.search(zz["xq"][:ns], nprobe, k)            # 7 queries: its direct path
+    assert assert_same_topk(D, I, zz["Ds_small"], zz["Is_small"], metric + " small batch") == 0
+    # add() of the stored vectors builds the reference's lists
+    g.reset()
+    assert g.ntotal == 0
+    g.add(zz["xb"])
+    for li in range(int(z["nlist"])):
+        o0, o1 = zz["list_offsets"][li], zz["list_offsets"][li + 1]
+        v, ids = g.get_list(li)
+        assert np.array_equal(ids, zz["ids"][o0:o1]) and np.array_equal(bits(v), bits(zz["vecs"][o0:o1]))
+    g.close()
+
+
+@pytest.mark.parametrize("name", ["flat_l2_d32", "flat_ip_d32", "flat_padding_ties_l2"])
+def test_add_builds_the_same_lists(name):
+    z = load(name)
+    ref = make_index(z)
+    k = int(z["k"])
+    D0, I0 = ref.search_preassigned(z["xq"], z["keys"], k)
+    g = make_index(z, lists=False)
+    xb = z["xb"]
+    half = xb.shape[0] // 2
+    g.reserve_memory(xb.shape[0] // 4)
+    g.add(xb[:half])                                     # two batches, default ids
+    g.add(xb[half:], np.arange(half, xb.shape[0], dtype=np.int64))
+    assert g.ntotal == xb.shape[0]
+    for li in range(int(z["nlist"])):
+        o0, o1 = z["list_offsets"][li], z["list_offsets"][li + 1]
+        assert g.list_length(li) == o1 - o0
+        v, ids = g.get_list(li)
+        assert np.array_equal(ids, z["ids"][o0:o1]) and np.array_equal(bits(v), bits(z["vecs"][o0:o1]))
+    D, I = g.search_preassigned(z["xq"], z["keys"], k)
+    assert np.array_equal(bits(D), bits(D0)) and np.array_equal(I, I0)
+    g.reclaim_memory()
+    D, I = g.search_preassigned(z["xq"], z["keys"], k)
+    assert np.array_equal(bits(D), bits(D0)) and np.array_equal(I, I0)
+    g.close()
+    ref.close()
+
+
+def test_add_preassigned_drops_negative_lists():
+    z = load("flat_l2_d128_long")
+    g = make_index(z, lists=False)
+    n = z["assign"].shape[0]
+    # the fixture's own assignment rebuilds its lists (the stored vectors in input order, ids = input positions)
+    order = np.argsort(z["ids"])
+    xb = z["vecs"][order]
+    g.add_preassigned(xb, z["assign"])
+    assert g.ntotal == n
+    D, I = g.search_preassigned(z["xq"], z["keys"], int(z["k"]))
+    assert assert_same_topk(D, I, z["D"], z["I"], "add_preassigned") == 0
+    # ... and negative list ids drop their vectors: ntotal grows by the kept ones, the ids stay ntotal + i
+    a = z["assign"].copy()
+    a[::3] = -1
+    kept = np.nonzero(a >= 0)[0]
+    g.add_preassigned(xb, a)
+    assert g.ntotal == n + kept.size
+    li = int(a[kept[0]])
+    _v, ids = g.get_list(li)
+    first = np.nonzero(z["assign"] == li)[0]
+    assert np.array_equal(ids, np.concatenate([first, n + kept[a[kept] == li]]))
+    g.close()
+
+
+def test_batch_independence():
+    z = load("flat_l2_d32")
+    g = make_index(z)
+    k = int(z["k"])
+    D0, I0 = g.search_preassigned(z["xq"], z["keys"], k)
+    xq, keys = np.tile(z["xq"], (7, 1)), np.tile(z["keys"], (7, 1))
+    D, I = g.search_preassigned(xq, keys, k)
+    assert np.array_equal(bits(D), np.tile(bits(D0), (7, 1))) and np.array_equal(I, np.tile(I0, (7, 1)))
+    g.close()
+
+
+def test_torch_device_buffers():
+    torch = pytest.importorskip("torch")
+    z = load("flat_ip_d32")
+    g = make_index(z)
+    k = int(z["k"])
+    g.set_stream(torch.cuda.current_stream().cuda_stream)
+    xq, keys = torch.from_numpy(z["xq"]).cuda(), torch.from_numpy(z["keys"]).cuda()
+    D = torch.empty((xq.shape[0], k), dtype=torch.float32, device="cuda")
+    I = torch.empty((xq.shape[0], k), dtype=torch.int64, device="cuda")
+    g.search_preassigned(xq, keys, k, D=D, I=I)
+    torch.cuda.synchronize()
+    assert assert_same_topk(D.cpu().numpy(), I.cpu().numpy(), z["D"], z["I"], "device buffers") == 0
+    g.close()
+
+
+def test_refusals():
+    z = load("flat_l2_d32")
+    g = make_index(z)
+    nq = z["xq"].shape[0]
+    with pytest.raises(vlq.VlqError) as e:
+        g.search_preassigned(z["xq"], z["keys"], 1025)
+    assert e.value.code == ERR_UNSUPPORTED
+    with pytest.raises(vlq.VlqError) as e:
+        g.search(z["xq"], 1025, 10)
+    assert e.value.code == ERR_UNSUPPORTED
+    with pytest.raises(vlq.VlqError) as e:
+        g.search_preassigned(z["xq"], np.zeros((nq, 1025), np.int64), 10)
+    assert e.value.code == ERR_UNSUPPORTED
+    bad = z["keys"].copy()
+    bad[3, 1] = int(z["nlist"])
+    with pytest.raises(vlq.VlqError) as e:
+        g.search_preassigned(z["xq"], bad, 10)
+    assert e.value.code == ERR_INVALID and "nlist" in str(e.value)
+    # the flag was consumed: the index goes on working
+    D, I = g.search_preassigned(z["xq"], z["keys"], int(z["k"]))
+    assert assert_same_topk(D, I, z["D"], z["I"], "after a bad key") == 0
+    with pytest.raises(ValueError):
+        vlq.GpuIVFFlat(8, 4, metric="cosine")
+    g.close()

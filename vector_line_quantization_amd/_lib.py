@@ -23,6 +23,12 @@ SYMBOLS = [
     "vlq_ivfpq_search_refined", "vlq_ivfpq_search_refined_preassigned",
     "vlq_ivfpq_set_polysemous_ht", "vlq_ivfpq_query_codes", "vlq_ivfpq_polysemous_stats",
     "vlq_ivfpq_set_metric", "vlq_ivfpq_get_metric",
+    # IVFFlat (vlq_ivfflat_t)
+    "vlq_ivfflat_create", "vlq_ivfflat_destroy", "vlq_ivfflat_set_stream", "vlq_ivfflat_set_coarse_centroids",
+    "vlq_ivfflat_set_lists", "vlq_ivfflat_add", "vlq_ivfflat_add_preassigned", "vlq_ivfflat_reserve_memory",
+    "vlq_ivfflat_reclaim_memory", "vlq_ivfflat_ntotal", "vlq_ivfflat_list_length", "vlq_ivfflat_get_list", "vlq_ivfflat_reset",
+    "vlq_ivfflat_coarse_search", "vlq_ivfflat_search", "vlq_ivfflat_search_preassigned", "vlq_ivfflat_stats",
+    "vlq_ivfflat_last_scan_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -86,6 +92,8 @@ def lib():
         L.vlq_last_error.restype = C.c_char_p
         L.vlq_ivfpq_ntotal.restype = C.c_int64
         L.vlq_ivfpq_destroy.restype = None
+        L.vlq_ivfflat_ntotal.restype = C.c_int64
+        L.vlq_ivfflat_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -299,6 +299,12 @@ bool launch_scan_ip(const ScanArgs& a, hipStream_t s);
 // (the reference's min-heap starts there, Heap.h:62-64)
 void launch_coarse_ip_finish(float* cdis, const int64_t* keys, int64_t n, hipStream_t s);
 
+// IVFFlat (IndexIVFFlat::search_knn_L2sqr / search_knn_inner_product, IndexIVF.cpp:272-370; scan_flat.hip): a.codes holds the
+// lists' vectors as rows of a.d floats; a.queries, a.keys, a.ids, a.list_off / a.list_len, a.D / a.I, a.ncode (distances
+// computed), a.bad_key, a.nq, a.nprobe, a.k, a.d, a.nlist are read, nothing else.  nlist_visited: += keys in 0 .. nlist-1.
+// Which instantiation, read path and LDS size serve a shape is plan_flat_scan's decision (flat_plan.h); false: not built.
+bool launch_scan_flat(const ScanArgs& a, bool inner_product, unsigned long long* nlist_visited, hipStream_t s);
+
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this
 inline size_t query_order_bins_padded(int nlist) {

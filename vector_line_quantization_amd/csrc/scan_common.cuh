@@ -10,7 +10,8 @@ namespace vlq {
 
 // Rows out: the selection's sorted keys -> (distance, label).  Scan positions are translated with
 // the prefix sums `cum`; resolve(p, lkey, loff): list id and list start offset of probe p.
-template <int KPL, typename Sel, typename Resolve>
+// NEG: the keys were ordered on negated values (inner products): every distance, the padding included, is negated back.
+template <int KPL, bool NEG = false, typename Sel, typename Resolve>
 __device__ __forceinline__ void emit_rows(const Sel& sel, const uint32_t* cum, const ScanArgs& a, int64_t q,
                                           int lane, Resolve resolve) {
 #pragma unroll
@@ -33,7 +34,7 @@ __device__ __forceinline__ void emit_rows(const Sel& sel, const uint32_t* cum, c
             const int64_t o = pos - cum[lo];
             id = a.store_pairs ? (lkey << 32 | o) : a.ids[loff + o];   // IndexIVFPQ.cpp:798
         }
-        a.D[q * a.k + e] = dis;
+        a.D[q * a.k + e] = NEG ? -dis : dis;
         a.I[q * a.k + e] = id;
     }
 }

@@ -348,6 +348,135 @@ class GpuIVFPQ:
         return {"coarse_ms": ms[0], "tables_ms": ms[1], "scan_ms": ms[2], "scan_calls": calls.value}
 
 
+class GpuIVFFlat:
+    """faiss::IndexIVFFlat / gpu::GpuIndexIVFFlat (IndexIVF.h:132-205, gpu/GpuIndexIVFFlat.h): inverted lists of the vectors
+    themselves, exact distances.  metric "l2": ascending squared distances, FLT_MAX / -1 padding; "ip": descending inner
+    products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfflat_*)."""
+
+    METRICS = GpuIVFPQ.METRICS
+
+    def __init__(self, d, nlist, device=0, metric="l2"):
+        self.d, self.nlist, self.device = d, nlist, device
+        self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        self.metric = metric
+        check(lib().vlq_ivfflat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist), C.c_int(self.METRICS[metric])))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_ivfflat_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    _out = GpuIVFPQ._out
+
+    # --- state ------------------------------------------------------------
+    def set_stream(self, stream_ptr):
+        check(lib().vlq_ivfflat_set_stream(self._h, C.c_void_p(stream_ptr or 0)))
+
+    def set_coarse_centroids(self, c):
+        p, _k = _ptr(c, np.float32)
+        check(lib().vlq_ivfflat_set_coarse_centroids(self._h, p))
+
+    def set_lists(self, vecs, ids, list_offsets):
+        """vecs [ntotal][d] float32 and ids [ntotal] in list-contiguous order, list_offsets [nlist + 1]"""
+        pv, _a = _ptr(vecs, np.float32)
+        pi, _b = _ptr(ids, np.int64)
+        po, _c = _ptr(list_offsets, np.int64)
+        check(lib().vlq_ivfflat_set_lists(self._h, pv, pi, po))
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_ivfflat_ntotal(self._h))
+
+    def list_length(self, i):
+        n = C.c_int64()
+        check(lib().vlq_ivfflat_list_length(self._h, C.c_int(i), C.byref(n)))
+        return n.value
+
+    def get_list(self, i):
+        n = self.list_length(i)
+        vecs = np.empty((n, self.d), np.float32)
+        ids = np.empty((n,), np.int64)
+        check(lib().vlq_ivfflat_get_list(self._h, C.c_int(i), vecs.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        return vecs, ids
+
+    def reset(self):
+        check(lib().vlq_ivfflat_reset(self._h))
+
+    # --- add --------------------------------------------------------------
+    def add(self, x, xids=None):
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        check(lib().vlq_ivfflat_add(self._h, C.c_int64(x.shape[0]), px, pi))
+
+    def add_preassigned(self, x, assign, xids=None):
+        """IndexIVFFlat::add_core with precomputed_idx: a negative list id drops the vector"""
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        pa, _c = _ptr(assign, np.int64)
+        check(lib().vlq_ivfflat_add_preassigned(self._h, C.c_int64(x.shape[0]), px, pi, pa))
+
+    def reserve_memory(self, num_vecs):
+        check(lib().vlq_ivfflat_reserve_memory(self._h, C.c_int64(num_vecs)))
+
+    def reclaim_memory(self):
+        n = C.c_uint64()
+        check(lib().vlq_ivfflat_reclaim_memory(self._h, C.byref(n)))
+        return n.value
+
+    # --- search -----------------------------------------------------------
+    def search(self, x, nprobe, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _b = _out_ptr(D, np.float32)
+        pI, _c = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfflat_search(self._h, C.c_int64(n), px, C.c_int(nprobe), C.c_int(k), pD, pI))
+        return D, I
+
+    def search_preassigned(self, x, keys, k, D=None, I=None):
+        n, nprobe = x.shape[0], keys.shape[1]
+        px, _a = _ptr(x, np.float32)
+        pk, _b = _ptr(keys, np.int64)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _d = _out_ptr(D, np.float32)
+        pI, _e = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfflat_search_preassigned(self._h, C.c_int64(n), px, pk, C.c_int(nprobe), C.c_int(k), pD, pI))
+        return D, I
+
+    def coarse_search(self, x, nprobe, cdis=None, keys=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        cdis = self._out(cdis, (n, nprobe), np.float32, x)
+        keys = self._out(keys, (n, nprobe), np.int64, x)
+        pc, _b = _out_ptr(cdis, np.float32)
+        pk, _c = _out_ptr(keys, np.int64)
+        check(lib().vlq_ivfflat_coarse_search(self._h, C.c_int64(n), px, C.c_int(nprobe), pc, pk))
+        return cdis, keys
+
+    # --- introspection ----------------------------------------------------
+    def stats(self, reset=False):
+        """IndexIVFFlatStats since the last reset: (nq, lists visited, distances computed)"""
+        nq, nl, nd = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().vlq_ivfflat_stats(self._h, C.byref(nq), C.byref(nl), C.byref(nd), C.c_int(int(reset))))
+        return nq.value, nl.value, nd.value
+
+    def last_scan_info(self):
+        """the kernel instantiation and read path of the last list scan (include/vlq_ivfpq.h)"""
+        buf = C.create_string_buffer(256)
+        check(lib().vlq_ivfflat_last_scan_info(self._h, buf, C.c_int(256)))
+        return buf.value.decode()
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
