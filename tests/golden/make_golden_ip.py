@@ -115,6 +115,12 @@ def ip_d30_m6():
     return spec(30, 12, 6, 6, 4, 10), mixture(2606, 30, 12, 2000, 1200, 40)
 
 
+@icase
+def ip_m24_d48():
+    """M 24 and d 48: a code of six words, read by three 8-byte loads; one list longer than two trips of the kernel."""
+    return spec(48, 24, 24, 8, 6, 10), mixture(2707, 48, 24, 3000, 2000, 40, heavy=600)
+
+
 def build_driver():
     subprocess.check_call(["make", "-s", "-f", "oracle/ref.mk"], cwd=ROOT)
     exe = os.path.join(OUT, "ip_driver")
@@ -235,6 +241,10 @@ def run_case(name):
             refuse(name, "needs a list longer than 512 codes and three empty lists (longest %d, %d empty)" % (lens.max(), (lens == 0).sum()))
         if not (lens[z["keys"][z["keys"] >= 0]] == 0).any():
             refuse(name, "no query probes an empty list")
+    if name == "ip_m24_d48":
+        kk = z["keys"][z["keys"] >= 0]
+        if not (lens[kk] > 512).any():
+            refuse(name, "no query probes a list longer than 512 codes (longest %d)" % lens.max())
     if name == "ip_padding_ties":
         cut = [(np.cumsum(lens[kq[kq >= 0]]) >= s["max_codes"]).argmax() + 1 < (kq >= 0).sum() if (np.cumsum(lens[kq[kq >= 0]]) >= s["max_codes"]).any() else False
                for kq in z["keys"]]

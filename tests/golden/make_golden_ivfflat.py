@@ -150,6 +150,26 @@ def flat_kwide():
     return spec("l2", 8, 1024, extra_k=(1,)), mixture(4506, 24, 8, 1500, 6)
 
 
+def _ragged(metric, d, seed):
+    """d > 32 with d % 32 != 0: the last 128-byte piece of a row is partial.  add_core with a given assignment (the nearest
+    centroid in L2, whatever the metric), so that the heavy centre's list is longer than two trips of the kernel's 256 lanes."""
+    cent, xb, xq = mixture(seed, d, 16, 1200, 20, heavy=560)
+    a = np.argmin(((xb[:, None, :].astype(np.float64) - cent[None].astype(np.float64)) ** 2).sum(-1), axis=1).astype(np.int64)
+    return spec(metric, 6, 10, assign=a), (cent, xb, xq)
+
+
+@case
+def flat_ragged_d36_l2():
+    """d 36: one whole piece and one of 16 bytes"""
+    return _ragged("l2", 36, 4707)
+
+
+@case
+def flat_ragged_d100_ip():
+    """d 100: three whole pieces and one of 16 bytes"""
+    return _ragged("ip", 100, 4708)
+
+
 def build_driver():
     subprocess.check_call(["make", "-s", "-f", "oracle/ref.mk"], cwd=ROOT)
     exe = os.path.join(OUT, "ivfflat_driver")
@@ -285,6 +305,10 @@ def run_case(name):
         kk = z["keys"][z["keys"] >= 0]
         if not (lens[kk] == 0).any() or not (lens[kk] >= 520).any():
             refuse(name, "no query probes an empty list / the long list")
+    if name.startswith("flat_ragged"):
+        kk = z["keys"][z["keys"] >= 0]
+        if d <= 32 or d % 32 == 0 or d % 4 != 0 or not (lens[kk] > 520).any():
+            refuse(name, "needs d > 32 with a partial last piece and a probed list longer than 520 vectors (longest %d)" % lens.max())
     if name.startswith("flat_padding_ties"):
         I, D, k = z["I"], z["D"], s["k"]
         if not ((I == -1).any(axis=1) & (I != -1).any(axis=1)).any():

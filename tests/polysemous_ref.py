@@ -83,3 +83,64 @@ def pairs_to_ids(case, P):
 def first_argmin_codes(tables):
     """q_code of tables [..., M, ksub]: the first minimum of every sub-quantizer's row"""
     return np.argmin(tables, axis=-1).astype(np.uint8)
+
+
+def oracle_qcodes(ox, xq, keys):
+    """q_code [nq][nprobe][M] of every (query, probe) from the oracle's tables alone: the first argmin of the table the
+    mode defines (csrc/scan_poly.hip, include/vlq_ivfpq.h).  Rows of keys outside 0 .. nlist-1 stay 0."""
+    nq, nprobe = keys.shape
+    out = np.zeros((nq, nprobe, ox.M), np.uint8)
+    F32 = np.float32
+    pt = ox.precomputed_table if ox.by_residual and ox.use_precomputed_table in (1, 2) else None
+    for i in range(nq):
+        live = [p for p in range(nprobe) if 0 <= keys[i, p] < ox.nlist]
+        if not live:
+            continue
+        if not ox.by_residual:
+            out[i, live] = first_argmin_codes(ox.distance_table(xq[i]))          # one code per query
+            continue
+        if pt is not None:
+            m2ip = (F32(-2) * ox.inner_prod_table(xq[i])).astype(F32)            # fvec_madd: one multiply, one add
+        for p in live:
+            key = int(keys[i, p])
+            if pt is None:                                                       # table type 0: the float32 residual's table
+                tab = ox.distance_table((xq[i] - ox.coarse_centroids[key]).astype(F32))
+            elif ox.imi_nbits:                                                   # table type 2: a row per half
+                k0, k1 = key & ((1 << ox.imi_nbits) - 1), key >> ox.imi_nbits
+                half = ox.M // 2
+                tab = np.concatenate([pt[k0][:half], pt[k1][half:]])
+                tab = (tab + m2ip).astype(F32)
+            else:
+                tab = (pt[key] + m2ip).astype(F32)
+            out[i, p] = first_argmin_codes(tab)
+    return out
+
+
+def oracle_scan(ox, xq, keys, coarse_dis):
+    """everything the filtered rows of a batch are made of, from the oracle alone: dict with qcodes, all_D / all_pairs (the
+    unfiltered distance and pair label of every scanned code: search_preassigned at k = the largest ncode, store_pairs), and
+    per query the scan order's pair labels, Hamming distances and ncode"""
+    qcodes = oracle_qcodes(ox, xq, keys)
+    scans = [scan_hamming(keys[i], qcodes[i], ox.codes, ox.list_offsets, ox.max_codes) for i in range(keys.shape[0])]
+    k_all = max(1, max(s[2] for s in scans))
+    all_D, all_pairs = ox.search_preassigned(xq, keys, coarse_dis, k_all, store_pairs=True)
+    return dict(qcodes=qcodes, all_D=all_D, all_pairs=all_pairs, pairs=[s[0] for s in scans], hd=[s[1] for s in scans],
+                ncode=np.array([s[2] for s in scans], np.int64))
+
+
+def oracle_filtered(scan, ht, k, rows=None):
+    """the restatement's rows over an oracle_scan: D, pair labels [n][k], passes per query [n], ncode per query [n]"""
+    rows = range(len(scan["pairs"])) if rows is None else rows
+    D, P, npass = [], [], []
+    for i in rows:
+        d, p, n = filtered_topk(scan["all_D"][i], scan["all_pairs"][i], scan["pairs"][i], scan["hd"][i], ht, k)
+        D.append(d); P.append(p); npass.append(n)
+    return np.array(D), np.array(P), np.array(npass, np.int64), scan["ncode"][list(rows)]
+
+
+def labels_to_ids(list_offsets, ids, P):
+    """stored ids of pair labels (-1 stays)"""
+    out = np.full(P.shape, -1, np.int64)
+    ok = P >= 0
+    out[ok] = ids[list_offsets[P[ok] >> 32] + (P[ok] & 0xFFFFFFFF)]
+    return out

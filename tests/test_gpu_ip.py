@@ -11,7 +11,8 @@ from util import GOLDEN, Case, assert_same_topk, bits
 
 pytestmark = pytest.mark.gpu
 ERR_UNSUPPORTED, ERR_STATE = 3, 4
-CASES = ["ip_residual", "ip_nonresidual", "ip_m16_d128", "ip_padding_ties", "ip_kwide", "ip_m20_d40", "ip_d30_m6"]
+CASES = ["ip_residual", "ip_nonresidual", "ip_m16_d128", "ip_padding_ties", "ip_kwide", "ip_m20_d40", "ip_d30_m6",
+         "ip_m24_d48"]
 NEG_FLT_MAX_BITS = np.float32(-np.finfo(np.float32).max).view(np.uint32)
 
 

@@ -11,7 +11,8 @@ from util import GOLDEN, assert_same_topk, bits
 pytestmark = pytest.mark.gpu
 ERR_INVALID, ERR_UNSUPPORTED = 1, 3
 CASES = ["flat_l2_d32", "flat_ip_d32", "flat_l2_d128_long", "flat_tail_d30_l2", "flat_tail_d30_ip", "flat_tail_d5_l2",
-         "flat_tail_d5_ip", "flat_tail_d3_l2", "flat_tail_d3_ip", "flat_padding_ties_l2", "flat_padding_ties_ip", "flat_kwide"]
+         "flat_tail_d5_ip", "flat_tail_d3_l2", "flat_tail_d3_ip", "flat_padding_ties_l2", "flat_padding_ties_ip", "flat_kwide",
+         "flat_ragged_d36_l2", "flat_ragged_d100_ip"]
 METRIC = {0: "ip", 1: "l2"}
 FLT_MAX = np.float32(np.finfo(np.float32).max)
 PAD_BITS = {"l2": FLT_MAX.view(np.uint32), "ip": np.float32(-FLT_MAX).view(np.uint32)}

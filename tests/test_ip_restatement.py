@@ -11,7 +11,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ip_ref  # noqa: E402
 from util import GOLDEN, assert_same_topk  # noqa: E402
 
-CASES = ["ip_residual", "ip_nonresidual", "ip_m16_d128", "ip_padding_ties", "ip_kwide", "ip_m20_d40", "ip_d30_m6"]
+CASES = ["ip_residual", "ip_nonresidual", "ip_m16_d128", "ip_padding_ties", "ip_kwide", "ip_m20_d40", "ip_d30_m6",
+         "ip_m24_d48"]
 
 
 def load(name):

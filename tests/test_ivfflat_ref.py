@@ -13,7 +13,8 @@ from util import GOLDEN, assert_same_topk
 
 DIR = os.path.join(GOLDEN, "ivfflat")
 NAMES = ["flat_l2_d32", "flat_ip_d32", "flat_l2_d128_long", "flat_tail_d30_l2", "flat_tail_d30_ip", "flat_tail_d5_l2",
-         "flat_tail_d5_ip", "flat_tail_d3_l2", "flat_tail_d3_ip", "flat_padding_ties_l2", "flat_padding_ties_ip", "flat_kwide"]
+         "flat_tail_d5_ip", "flat_tail_d3_l2", "flat_tail_d3_ip", "flat_padding_ties_l2", "flat_padding_ties_ip", "flat_kwide",
+         "flat_ragged_d36_l2", "flat_ragged_d100_ip"]
 METRIC = {0: "ip", 1: "l2"}
 
 
@@ -69,6 +70,14 @@ def test_long_list_fixture_shape():
     kk = z["keys"][z["keys"] >= 0]
     assert lens.max() >= 520 and (lens == 0).sum() >= 2
     assert (lens[kk] == 0).any() and (lens[kk] >= 520).any()
+
+
+@pytest.mark.parametrize("name", ["flat_ragged_d36_l2", "flat_ragged_d100_ip"])
+def test_ragged_fixture_shape(name):
+    z = load(name)
+    d, lens = int(z["d"]), np.diff(z["list_offsets"])
+    assert d > 32 and d % 32 != 0 and d % 4 == 0          # the tile path with a partial last piece
+    assert (lens[z["keys"][z["keys"] >= 0]] > 520).any()
 
 
 @pytest.mark.parametrize("metric", ["l2", "ip"])
