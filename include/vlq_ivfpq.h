@@ -161,7 +161,14 @@ int vlq_ivfpq_coarse_screen_state(vlq_ivfpq_t h, int* enabled, uint64_t* rows, u
  * like vlq_ivfpq_search_preassigned below; max_codes must be 0 then), k <= 1024.
  * Host D / I: the call returns with the rows in place.  PAGE-LOCKED host D / I (hipHostMalloc / hipHostRegister:
  * what GpuResources::getPinnedMemory hands out, gpu/GpuResources.h:40) are written by the scan kernel itself --
- * no staging buffer, no copy-out; pageable ones are staged through device memory and copied. */
+ * no staging buffer, no copy-out; pageable ones are staged through device memory and copied.
+ * Pages: a call is served in pages of at most 32 768 queries (GpuIndex::search, gpu/GpuIndex.cu:29,108-147; the coarse
+ * stage in fewer where its [page][nlist] distance matrix would pass 8 GiB), each with the scan kernel that suits the page's
+ * own size.  The rows, the counters and the errors of a call do not depend on how it is paged: a query's row is the same
+ * bits in any batch.  The one thing the reference takes from the batch size -- knn_L2sqr's direct distances for n < 20
+ * (utils.cpp:935-946) -- is taken from the call's n, never from a page's, in every search entry point of this header (a
+ * last page of 7 queries of a 32 775-query call gets the matrix formulation).  The VLQ searches of vlq_line.h have no such
+ * dispatch: every n gets the matrix formulation there. */
 int vlq_ivfpq_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe, int k,
                      float* D, int64_t* I);
 

@@ -28,6 +28,15 @@ static ScanShape multi_index(int M) {       // 2 x 8 bits: 65 536 cells for 1 M 
     s.imi_nbits = 8; s.nlist = 65536; s.have_rank = false;
     return s;
 }
+// the last page of a call of 32 768 + r queries on a small index of 16-byte codes (tests/test_gpu_query_pages.py): 64 lists,
+// 4000 vectors (neither short nor long lists), nprobe 32, k 10; M = 8: the same over d = 32 with nprobe 8, as that file's
+// "scanm" index is searched
+static ScanShape tail_page(int64_t r, int M = 16, int d = 128, int nprobe = 32) {
+    ScanShape s = code_size(M, d);
+    s.nlist = 64; s.ntotal = 4000; s.nprobe = nprobe;
+    s.n = 32768 + r; s.ni = r;
+    return s;
+}
 static ScanShape with(ScanShape s, const std::function<void(ScanShape&)>& f) { f(s); return s; }
 
 static std::string kernel_name(const ScanShape& s, const vlq::ScanPlan& p) {
@@ -89,6 +98,14 @@ int main() {
         {"walk_first_forced_off", with(headline(), [](ScanShape& s) { s.walk_first = -1; })},
         {"table_mode_0", with(headline(), [](ScanShape& s) { s.table_mode = 0; })},
         {"table_mode_2", with(headline(), [](ScanShape& s) { s.table_mode = 2; })},
+        {"tail_page_1", tail_page(1)},
+        {"tail_page_7", tail_page(7)},
+        {"tail_page_100", tail_page(100)},
+        {"tail_page_1100", tail_page(1100)},
+        {"tail_page_1500", tail_page(1500)},
+        {"tail_page_3100", tail_page(3100)},
+        {"tail_page_1500_m8", tail_page(1500, 8, 32, 8)},
+        {"tail_page_3100_m8", tail_page(3100, 8, 32, 8)},
     };
     for (const auto& [name, s] : shapes) {
         const vlq::ScanPlan p = vlq::plan_scan(s);

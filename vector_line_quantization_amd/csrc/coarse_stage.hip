@@ -335,13 +335,15 @@ static int imi_page(vlq_ivfpq_t h, int64_t n, const float* x_dev, int k, float* 
     return VLQ_OK;
 }
 
-int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev,
-               int64_t* keys_dev) {
+// n_call: the queries of the whole call when x_dev holds n of them (a caller that pages by itself: search_refined_dev).  The
+// reference hands its quantizer the whole batch, so the small-batch dispatch below is the call's, never the page's.
+int coarse_dev_of_call(vlq_ivfpq_t h, int64_t n, int64_t n_call, const float* x_dev, int nprobe, float* cdis_dev,
+                       int64_t* keys_dev) {
     const bool ip = h->metric == 0, imi = !ip && h->imi_nbits > 0;
     if (ip) TRY(ip_unsupported(h));
     StageTimer tm(h, 0);
     // knn_L2sqr dispatch (utils.cpp:935-946): small batches bypass the GEMM formulation
-    const bool direct = !ip && !imi && (h->d % 4 == 0) && n < 20;
+    const bool direct = !ip && !imi && (h->d % 4 == 0) && n_call < 20;
     // a 1-NN assignment writes no distance matrix: full pages whatever nlist is; a multi-index: its two [page][kc] tables
     int64_t page = (nprobe == 1 && !direct && vlq::coarse_argmin_ok(h->nlist, h->d)) ? 32768 : query_page(h);
     if (imi) page = std::max<int64_t>(1, std::min<int64_t>(32768, (int64_t)((size_t(1) << 29) >> h->imi_nbits)));
@@ -356,6 +358,11 @@ int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* 
     }
     tm.stop();
     return VLQ_OK;
+}
+
+int coarse_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, int nprobe, float* cdis_dev,
+               int64_t* keys_dev) {
+    return coarse_dev_of_call(h, n, n, x_dev, nprobe, cdis_dev, keys_dev);
 }
 
 // Spatial order of the lists (speed only): recursive two-means bisection of the centroids; lists

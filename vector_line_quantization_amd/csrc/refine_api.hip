@@ -2,6 +2,11 @@
 #include "handle.h"
 #include "lists.h"
 
+namespace vlq_detail {
+// coarse_stage.hip: coarse_dev for n queries of a call of n_call (the reference's small-batch dispatch is taken from n_call)
+int coarse_dev_of_call(vlq_ivfpq_t h, int64_t n, int64_t n_call, const float* x_dev, int nprobe, float* cdis_dev, int64_t* keys_dev);
+}  // namespace vlq_detail
+
 extern "C" {
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -148,7 +153,8 @@ static int search_refined_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const i
         const int64_t* ki = kd ? kd + i0 * nprobe : h->ws_keys.as<int64_t>();
         const float* ci = kd ? cd + i0 * nprobe : h->ws_cdis.as<float>();
         h->order_hist_ready = false;
-        if (!kd) TRY(coarse_dev(h, ni, xi, nprobe, h->ws_cdis.as<float>(), h->ws_keys.as<int64_t>()));   // IndexIVFPQ.cpp:1371
+        // IndexIVFPQ.cpp:1371 searches the quantizer once with the whole batch: direct or GEMM distances by n, not by the page
+        if (!kd) TRY(coarse_dev_of_call(h, ni, n, xi, nprobe, h->ws_cdis.as<float>(), h->ws_keys.as<int64_t>()));
         TRY(scan_runs_dev(h, ni, xi, ki, ci, nprobe, kc, h->ws_Dsl.as<float>(), h->ws_sl.as<int64_t>(), 1));   // :1378-1385
         TRY(refine_dev(h, ni, xi, h->ws_sl.as<int64_t>(), kc, k, Dd + i0 * k, Id + i0 * k));                // :1392-1444
     }
