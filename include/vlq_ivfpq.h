@@ -156,6 +156,22 @@ int vlq_ivfpq_set_scan_schedule(vlq_ivfpq_t h, int mode);
 int vlq_ivfpq_set_coarse_screen(vlq_ivfpq_t h, int mode);
 int vlq_ivfpq_coarse_screen_state(vlq_ivfpq_t h, int* enabled, uint64_t* rows, uint32_t* undecided);
 
+/* Stored table sums of the 16-byte list scan -- SPEED AND MEMORY ONLY, results are identical with and without them
+ * (csrc/scan16.hip, csrc/scan_sum_bound.h).  For 16 x 8-bit codes, d = 128, precomputed table, flat coarse quantizer, lists of
+ * 24 .. 1023 codes on average, the handle keeps 4 bytes per stored code: the sum of the code's 16 entries of its list's
+ * precomputed-table row.  Searches with k <= 32 whose batch gives every query a workgroup of its own then select on
+ * (coarse distance + stored sum) + the 16 entries of the per-query table -- no table row per probe -- and redo in the
+ * reference's arithmetic only the few codes within a rigorous rounding bound of the k-th value.  A query the bound cannot
+ * decide is scanned again on stored rows; a handle where that happens to more than 1 / 8 of a batch's queries goes back to
+ * stored rows until its lists or quantizers change.
+ *   mode 0: stored rows, 1: automatic (the default).
+ * vlq_ivfpq_scan_sums_state: *enabled = the switch is on and the handle has not dropped the loop, *queries_seen = queries
+ * scanned by it, *undecided = those redone on stored rows, *finalists = codes redone exactly (as of the last batch whose
+ * counters have reached the host).  vlq_ivfpq_last_scan_info ends in rows=sums or rows=stored.
+ * Replaces nothing in the reference (its scan adds table entries only, IndexIVFPQ.cpp:788-794). */
+int vlq_ivfpq_set_scan_sums(vlq_ivfpq_t h, int mode);
+int vlq_ivfpq_scan_sums_state(vlq_ivfpq_t h, int* enabled, uint64_t* queries_seen, uint64_t* undecided, uint64_t* finalists);
+
 /* IndexIVFPQ::search (IndexIVFPQ.cpp:1063-1081) = GpuIndexIVFPQ::search.
  * x[n*d], D[n*k], I[n*k]   [h|d].   nprobe <= 1024 (multi-index quantizer: <= VLQ_MAX_IMI_NPROBE, scanned in runs of 1024
  * like vlq_ivfpq_search_preassigned below; max_codes must be 0 then), k <= 1024.

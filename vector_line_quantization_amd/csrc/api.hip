@@ -86,6 +86,7 @@ int StagedRows::finish(vlq_ivfpq_t h) {
 static int finish_index_build(vlq_ivfpq_t h) {
     if (!(h->have_coarse && h->have_pq)) return VLQ_OK;
     TRY(ensure_term2(h));
+    (void)ensure_code_sums(h);      // (none for this index, or no memory for them: the search runs on stored rows)
     vlq::preload_search_kernels();
     return VLQ_OK;
 }
@@ -180,6 +181,7 @@ void vlq_ivfpq_destroy(vlq_ivfpq_t h) {
     drain_profile(h);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->screen_cnt_host) (void)hipHostFree(h->screen_cnt_host);
+    if (h->sums_cnt_host) (void)hipHostFree(h->sums_cnt_host);
     const hipEvent_t fork = h->imi_fork, join = h->imi_join;
     const hipStream_t imi_stream = h->imi_stream, own_stream = h->own_stream;
     delete h;       // every DevBuf of the handle frees its block here: before the streams below are destroyed
@@ -229,6 +231,7 @@ int vlq_ivfpq_set_coarse_centroids(vlq_ivfpq_t h, const float* centroids) {
     h->imi_nbits = 0;
     h->term2_valid = false;
     h->term2h_valid = false;
+    sums_invalidate(h);
     h->coarse_s_stride = 0;          // the sampled tiles belong to the old centroids
     return VLQ_OK;
 }
@@ -263,6 +266,7 @@ int vlq_ivfpq_set_imi_centroids(vlq_ivfpq_t h, int imi_nbits, const float* centr
     h->have_coarse = true;
     h->term2_valid = false;
     h->term2h_valid = false;
+    sums_invalidate(h);
     return VLQ_OK;
 }
 
@@ -283,6 +287,7 @@ int vlq_ivfpq_set_pq_centroids(vlq_ivfpq_t h, const float* centroids) {
     h->have_pq = true;
     h->term2_valid = false;
     h->term2h_valid = false;
+    sums_invalidate(h);
     return VLQ_OK;
 }
 
@@ -309,8 +314,10 @@ int vlq_ivfpq_set_metric(vlq_ivfpq_t h, int metric) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->term2.release();
         h->term2h.release();
+        h->code_sums.release();
         h->term2_valid = false;
         h->term2h_valid = false;
+        sums_invalidate(h);
     }
     h->metric = metric;
     // back to L2: what vlq_ivfpq_set_lists / vlq_ivfpq_add would have built by now
@@ -348,6 +355,24 @@ int vlq_ivfpq_coarse_screen_state(vlq_ivfpq_t h, int* enabled, uint64_t* rows, u
     if (enabled) *enabled = (h->metric != 0 && h->coarse_screen && (h->imi_nbits > 0 ? (h->imi_screen[0].ok && h->imi_screen[1].ok) : h->screen.ok)) ? 1 : 0;
     if (rows) *rows = h->screen_rows_seen;
     if (undecided) *undecided = h->screen_cnt_host ? *h->screen_cnt_host : 0u;
+    return VLQ_OK;
+}
+
+int vlq_ivfpq_set_scan_sums(vlq_ivfpq_t h, int mode) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (mode != 0 && mode != 1) return fail(VLQ_ERR_INVALID, "scan sums mode %d (0 = stored rows, 1 = automatic)", mode);
+    h->scan_sums = mode;
+    return VLQ_OK;
+}
+
+int vlq_ivfpq_scan_sums_state(vlq_ivfpq_t h, int* enabled, uint64_t* queries_seen, uint64_t* undecided, uint64_t* finalists) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (h->sums_cnt_host) { TRY(set_dev(h)); HIP_TRY(hipStreamSynchronize(h->stream)); }     // the mirror is up to date after this
+    sums_defeated(h);
+    if (enabled) *enabled = (h->scan_sums != 0 && !h->sums_dropped) ? 1 : 0;
+    if (queries_seen) *queries_seen = h->sums_q_copied;
+    if (undecided) *undecided = h->sums_cnt_host ? h->sums_cnt_host[0] : 0;
+    if (finalists) *finalists = h->sums_cnt_host ? h->sums_cnt_host[1] : 0;
     return VLQ_OK;
 }
 
@@ -429,6 +454,7 @@ int vlq_ivfpq_set_lists(vlq_ivfpq_t h, const uint8_t* codes, const int64_t* ids,
     h->h_lists_stale = false;
     h->ntotal = ntotal;
     h->have_lists = true;
+    sums_invalidate(h);
     return finish_index_build(h);
 }
 
@@ -654,9 +680,9 @@ int vlq_ivfpq_last_scan_info(vlq_ivfpq_t h, char* buf, int cap) {
         HIP_TRY(hipMemcpy(ws, h->walk_state.p, sizeof(ws), hipMemcpyDeviceToHost));
         period = ws[0]; launch_period = ws[1];
     }
-    snprintf(buf, (size_t)cap, "kernel=%s order=%s first=%d shared=%d/%d limit=%d period_ticks=%d launch_period_ticks=%d placement=%s",
+    snprintf(buf, (size_t)cap, "kernel=%s order=%s first=%d shared=%d/%d limit=%d period_ticks=%d launch_period_ticks=%d placement=%s rows=%s",
              h->last_scan[0] ? h->last_scan : "none", order, h->last_walk_first, shared, h->last_walk_samples, h->last_walk_limit, period,
-             launch_period, h->last_placement);
+             launch_period, h->last_placement, h->last_rows_sums ? "sums" : "stored");
     return VLQ_OK;
 }
 
@@ -784,6 +810,9 @@ int vlq_ivfpq_add(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* xids)
                           h->have_rpq ? h->ws_rcodes.as<uint8_t>() : nullptr, (const int64_t*)idd, h->ntotal, h->stream));
     if (h->have_rpq) h->have_rcodes = true;
     h->ntotal += n;                                             // IndexIVFPQ.cpp:271
+    // (the whole array is rebuilt, also after an append that fitted the lists' slack: one pass over the codes, 16 bytes read
+    // per stored vector -- rebuilding only the new slots is left for when an add-heavy workload shows up in a profile)
+    sums_invalidate(h);
     return finish_index_build(h);
 }
 
@@ -791,6 +820,7 @@ int vlq_ivfpq_reserve_memory(vlq_ivfpq_t h, int64_t num_vecs) {
     if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument");
     TRY(set_dev(h));
     vlq::ListStore ls = list_store(h);
+    sums_invalidate(h);
     return vlq::lists_reserve(ls, num_vecs, h->stream);
 }
 
@@ -798,6 +828,7 @@ int vlq_ivfpq_reclaim_memory(vlq_ivfpq_t h, uint64_t* bytes_reclaimed) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     TRY(set_dev(h));
     vlq::ListStore ls = list_store(h);
+    sums_invalidate(h);
     return vlq::lists_reclaim(ls, bytes_reclaimed, h->stream);
 }
 

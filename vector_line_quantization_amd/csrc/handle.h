@@ -157,6 +157,18 @@ struct vlq_ivfpq_s {
     bool fp16_tables = false, term2h_valid = false;
     DevBuf term2h, ws_qtabh;
     DevBuf stats;   // [0] ncode (u64), [1] bad key flag (int)
+    // Stored table sums of the 16-byte scan (scan16.hip, scan_sum_bound.h): one float per code slot of `codes` (the code's 16
+    // term-2 entries added up) and one per list (t2abs).  They depend on the codebooks, the centroids and the list layout:
+    // whatever changes one of those calls sums_invalidate(), ensure_code_sums() (scan_stage.hip) rebuilds them -- with the
+    // lists' arrival, and lazily before a scan.  scan_sums: 0 = stored rows, 1 = automatic (vlq_ivfpq_set_scan_sums).
+    // sums_dropped: too many of a batch's queries were undecided (kSumsDropNum / kSumsDropDen, scan_stage.hip); the handle
+    // stays on stored rows until its lists or quantizers change.  The device counters {undecided queries, finalists} are
+    // mirrored into page-locked memory behind each batch, like the coarse screen's.
+    DevBuf code_sums, t2abs, sums_cnt;
+    bool sums_valid = false, sums_dropped = false, last_rows_sums = false;
+    int scan_sums = 1;
+    unsigned long long* sums_cnt_host = nullptr;      // [2]
+    uint64_t sums_q_seen = 0, sums_q_copied = 0, sums_q_base = 0, sums_und_base = 0;
     // polysemous filtering (IndexIVFPQ::polysemous_ht, IndexIVFPQ.h:41): 0 = off; codes that passed the filter (u64, device)
     int polysemous_ht = 0;
     DevBuf poly_stats, ws_qcodes;
@@ -203,6 +215,9 @@ struct StageTimer {      // books the stream time between its construction and s
 };
 void drain_profile(vlq_ivfpq_t h);
 int ensure_term2(vlq_ivfpq_t h);
+inline void sums_invalidate(vlq_ivfpq_t h) { h->sums_valid = false; h->sums_dropped = false; }
+bool ensure_code_sums(vlq_ivfpq_t h);     // true: the stored sums are valid and the scan may use them
+void sums_defeated(vlq_ivfpq_t h);        // drops the stored-sums loop when the last batches' undecided share says so
 int scan_poly_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t* keys_dev, const float* cdis_dev, int nprobe, int k,
                   float* D_dev, int64_t* I_dev, int store_pairs, uint8_t* qcodes);
 int scan_runs_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const int64_t* kd, const float* cd, int nprobe, int k, float* Dd,

@@ -134,6 +134,11 @@ void launch_coarse_select(const float* dist, int64_t nq, int nlist, int nprobe, 
 void launch_pq_tables(const float* x, int64_t nv, int d, const float* cent, int M, int ksub,
                       int dsub, const float* rnorm, int mode, float* out, hipStream_t s);
 
+// stored table sums of the 16-byte scan (scan16.hip, scan_sum_bound.h): sums[slot] = the code's 16 term-2 entries added left to
+// right, slot = the code's place in `codes`; t2abs[list] = sum_m max_c |term2[list][m][c]|, rounded up.  M = 16, ksub = 256.
+void launch_code_sums(const uint8_t* codes, const int64_t* list_off, const int64_t* list_len, int nlist, const float* term2,
+                      float* sums, float* t2abs, hipStream_t s);
+
 // one visited probe of a query as the second build of the list-owned schedule reads it (scan16o.hip)
 struct OwnRec {
     int32_t key;      // list id
@@ -204,6 +209,11 @@ struct ScanArgs {
     // float16 look-up tables (scan16h.hip): half(term2) [nlist][M*ksub] and half(-2 <q_m, cent_mj>) [nq][M*ksub]
     const uint16_t* term2h = nullptr;
     const uint16_t* qtabh = nullptr;
+    // stored table sums (scan16_kernel's second probe loop, scan_sum_bound.h): code_sums[slot] per code slot of `codes`, t2abs[list];
+    // nullptr = the stored-rows loop.  sums_cnt: [0] += queries the sums could not decide, [1] += finalists done exactly
+    const float* code_sums = nullptr;
+    const float* t2abs = nullptr;
+    unsigned long long* sums_cnt = nullptr;
 };
 void launch_scan(const ScanArgs& a, hipStream_t s);
 // The engineered scan kernels.  Which of them serves a page, in which instantiation and with how much LDS is plan_scan's

@@ -19,6 +19,7 @@
 #include "sse_order.cuh"
 #include "wave_topk.cuh"
 #include "scan_common.cuh"
+#include "scan_sum_bound.h"
 
 namespace vlq {
 
@@ -1158,6 +1159,50 @@ void launch_pq_tables(const float* x, int64_t nv, int d, const float* cent, int 
     dim3 grid((unsigned)((nv + kTableVT - 1) / kTableVT), (unsigned)M, (unsigned)((ksub + kch - 1) / kch));
     hipLaunchKernelGGL(pq_tables_kernel, grid, dim3(256), smem, s, x, nv, d, cent, M, ksub, dsub,
                        rnorm, mode, out, kch);
+}
+
+// ---------------------------------------------------------------------------
+// Stored table sums of the 16-byte scan (scan16.hip, scan_sum_bound.h), one workgroup per list:
+//   sums[slot] = t2[0][c0] + t2[1][c1] + ... + t2[15][c15]   fp32, unfused, left to right, from the list's term-2 row
+//   t2abs[list] = sum_m max_c |t2[m][c]|, rounded up
+// The values depend on the query in no way; they are rebuilt when the lists or the quantizers change.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void code_sums_kernel(const uint8_t* __restrict__ codes, const int64_t* __restrict__ list_off,
+                                                        const int64_t* __restrict__ list_len, const float* __restrict__ term2,
+                                                        float* __restrict__ sums, float* __restrict__ t2abs) {
+    __shared__ uint32_t smax[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t list = blockIdx.x;
+    const float* row = term2 + (size_t)list * 4096;
+    for (int m = wave; m < 16; m += 4) {
+        // bit patterns of |x| order like the values and put a NaN above everything: it reaches t2abs
+        uint32_t v = 0;
+        for (int c = lane; c < 256; c += 64) v = max(v, __float_as_uint(row[m * 256 + c]) & 0x7fffffffu);
+        for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+        if (lane == 0) smax[m] = v;
+    }
+    __syncthreads();
+    if (t == 0) {
+        float s = 0.f;
+        for (int m = 0; m < 16; m++) s = scan_sum_up(__fadd_rn(s, __uint_as_float(smax[m])));
+        t2abs[list] = s;
+    }
+    const int64_t off = list_off[list], len = list_len[list];
+    const uint4* cp = reinterpret_cast<const uint4*>(codes) + off;
+    for (int64_t j = t; j < len; j += 256) {
+        const uint4 cc = cp[j];
+        const uint32_t w[4] = {cc.x, cc.y, cc.z, cc.w};
+        float s = row[w[0] & 255u];
+#pragma unroll
+        for (int m = 1; m < 16; m++) s = __fadd_rn(s, row[m * 256 + ((w[m >> 2] >> (8 * (m & 3))) & 255u)]);
+        sums[off + j] = s;
+    }
+}
+
+void launch_code_sums(const uint8_t* codes, const int64_t* list_off, const int64_t* list_len, int nlist, const float* term2,
+                      float* sums, float* t2abs, hipStream_t s) {
+    if (nlist <= 0) return;
+    hipLaunchKernelGGL(code_sums_kernel, dim3((unsigned)nlist), dim3(256), 0, s, codes, list_off, list_len, term2, sums, t2abs);
 }
 
 // ---------------------------------------------------------------------------

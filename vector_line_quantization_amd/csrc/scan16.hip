@@ -26,6 +26,7 @@
 #include "scan_common.cuh"
 #include "scan16_common.cuh"
 #include "placement_key.h"
+#include "scan_sum_bound.h"
 #include "walk_order.cuh"
 #include "wave_topk.cuh"
 
@@ -66,8 +67,13 @@ namespace vlq {
 // IMI: table type 2 (multi-index: two term2 rows per list) -- a compile-time switch, the row
 // addressing sits in the per-probe prefetch
 // OWNED: the list-owned schedule (kernels.h): the workgroup is one (query, list partition) item
-template <int KPL, int NW, int NBUF, bool PIPE, bool IMI, bool OWNED = false>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL == 4 || KPL == 2) && PIPE) || (NW == 2 && KPL <= 2)) ? 4 : 1))) void scan16_kernel(ScanArgs a, int lut_region) {
+// SUMS: the build with the stored-sums probe loop in front of the stored-rows loop (launched when ScanArgs::code_sums is set).
+// A build of its own, not a run-time branch of the one kernel: the two-wave shape holds 127 of its 128 VGPRs and one of its
+// two lanes' worth of spilled scalars; with both loops in one function the stored-rows loop reloaded two table registers from
+// scratch in every probe (its 66 spilled scalars took a second VGPR) -- for every caller, sums or not.  As a separate build
+// the stored-rows callers run the code they ran before, and in the SUMS build that loop is only the rare fallback.
+template <int KPL, int NW, int NBUF, bool PIPE, bool IMI, bool OWNED = false, bool SUMS = false>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SUMS && NW == 4) ? 5 : (((KPL == 4 || KPL == 2) && PIPE) || (NW == 2 && KPL <= 2)) ? 4 : 1))) void scan16_kernel(ScanArgs a, int lut_region) {
     constexpr int E = 4096;
     constexpr int NT = 64 * NW;       // threads per workgroup
     constexpr int NI = 16 / NW;       // float4 of the LUT per thread
@@ -85,7 +91,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
     // list ids / coarse distances permuted in place in pm -- so that the probe loop reads probe i's five values at index i
     // in one LDS round trip instead of ord[i] -> p -> pm.*[p] in two (the round trips wait behind the CU's gathers)
     const bool recs = a.nprobe <= 64;
-    int64_t* w_off = reinterpret_cast<int64_t*>((reinterpret_cast<uintptr_t>(wg_thr + 1) + 7) & ~(uintptr_t)7);   // [nprobe]
+    // the stored-sums loop's eight words (in the carve's slack, scan_plan.h): [0] max over the live probes of |dis0| + t2abs[list],
+    // [1 + w] wave w's share of sum_m max_c |q[m][c]|, [5] the query's verdict (1 = undecided)
+    float* sx = reinterpret_cast<float*>(wg_thr + 1);
+    int64_t* w_off = reinterpret_cast<int64_t*>((reinterpret_cast<uintptr_t>(sx + 8) + 7) & ~(uintptr_t)7);   // [nprobe]
     uint32_t* w_pos = reinterpret_cast<uint32_t*>(w_off + a.nprobe);                                              // [nprobe]
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -149,6 +158,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
     VLQ_PH(9);
     float4 m2t3[NI];
     load_query_table16<NI>(a, q, t, lane, wave, m2t3);
+    // The stored-sums loop (scan_sum_bound.h): the per-query table -2 <x_m, .> goes to LDS ONCE and serves
+    // every probe; a code's distance is approximated by A = (dis0 + code_sums[slot]) + its 16 table entries, the selection runs
+    // on A, and only the few codes within the error bound of the k-th A are redone in the reference's arithmetic at the end.
+    // Whole-query workgroups of the one-buffer shapes only (launch_scan16_t).
+    static_assert(!SUMS || (!PIPE && KPL == 1 && NBUF == 1 && !IMI && !OWNED), "the stored-sums loop is built for the one-buffer shapes");
+    constexpr bool sums_on = SUMS;
+    if (sums_on) {
+        // sum_m max_c |q[m][c]|: float4 i of this wave belongs to sub-quantizer NW * i + wave; the bit pattern of |x| orders
+        // like the value and carries a NaN to the top
+        float qs = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            reinterpret_cast<float4*>(lut)[i * NT + t] = m2t3[i];
+            uint32_t v = max(max(__float_as_uint(m2t3[i].x) & 0x7fffffffu, __float_as_uint(m2t3[i].y) & 0x7fffffffu),
+                             max(__float_as_uint(m2t3[i].z) & 0x7fffffffu, __float_as_uint(m2t3[i].w) & 0x7fffffffu));
+            v = wave_max_u32(v);
+            qs = scan_sum_up(__fadd_rn(qs, __uint_as_float(v)));
+        }
+        if (lane == 0) sx[1 + wave] = qs;
+    }
     WalkPre wpre;
     if (!OWNED && wave == 0) wpre = walk_prefetch(a, lane);       // in flight across the barrier and the prefix sums
     VLQ_PH(10);
@@ -168,6 +197,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
             nl += __popcll(mask);
         }
         VLQ_PH(12);
+        if (sums_on) {       // max over the live probes of |dis0| + t2abs[list] (pm.* still by probe index here)
+            uint32_t bm = 0;
+            for (int p0 = 0; p0 < nl; p0 += 64) {
+                if (p0 + lane < nl) {
+                    const int p = ord[p0 + lane];
+                    bm = max(bm, __float_as_uint(scan_sum_up(__fadd_rn(fabsf(pm.pd0[p]), a.t2abs[pm.pkey[p]]))) & 0x7fffffffu);
+                }
+            }
+            bm = wave_max_u32(bm);
+            if (lane == 0) sx[0] = __uint_as_float(bm);
+        }
         if (!OWNED && nparts == 1) walk_mean = walk_order_sort(a, pm, ord, nl, lane, wpre);    // parts are merged in part order = scan order
         if (recs) {
             const int p = lane < nl ? ord[lane] : 0;
@@ -265,6 +305,189 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
     auto prefetch = [&](int i) { prefetch_meta(i); prefetch_loads(i); };
     const int i_begin = (int)((int64_t)part * nlive / nparts), i_end = (int)((int64_t)(part + 1) * nlive / nparts);
     const unsigned long long t_walk = wall_clock64();
+    uint64_t nscan = 0;
+    if (SUMS) {
+        float qabs = sx[1];
+#pragma unroll
+        for (int w = 1; w < NW; w++) qabs = scan_sum_up(__fadd_rn(qabs, sx[1 + w]));
+        // B and eps of scan_sum_bound.h for every live probe of the query at once (wave-uniform)
+        const float B = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scan_sum_up(__fadd_rn(sx[0], qabs)))));
+        const float eps = scan_sum_bound(B);
+        // a NaN, an infinity or a magnitude near the end of the range: A could overflow where D does not -- stored rows
+        if (B < 1.0e38f) {
+            // Admission with slack: a candidate is rejected only above (current k-th A) + 3 eps >= (final k-th A) + 3 eps, and
+            // the finalists below are the keys at or under (final k-th A) + 2.25 eps.  The quarter-eps margins on both sides
+            // cover the rounding of the two sums (2^-23 of about B against eps / 4 = 2^-20 B).
+            sel.slack = __fmul_rn(3.f, eps);
+            float sr[3] = {0.f, 0.f, 0.f};
+            const uint4* codes4 = reinterpret_cast<const uint4*>(a.codes);
+            // this thread's code of trip c of the prefetched list and the code's stored sum (same slot), clamped
+            auto load_chunk_s = [&](auto cc_) {
+                constexpr int C = decltype(cc_)::value;
+                const int64_t idx = n_off + min((uint32_t)t + C * NT, n_len - 1);
+                cr[C] = codes4[idx];
+                sr[C] = a.code_sums[idx];
+            };
+            prefetch_meta(i_begin);
+            if (i_begin < nlive) {
+                load_chunk_s(std::integral_constant<int, 0>{});
+                load_chunk_s(std::integral_constant<int, 1>{});
+                if (NPRE == 3) load_chunk_s(std::integral_constant<int, 2>{});
+            }
+            const uint32_t w64 = (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 64;
+            for (int i = i_begin; i < i_end; i++) {      // no row, no table build, no workgroup barrier
+                const uint32_t len = n_len;
+                const float dis0 = n_dis0;
+                const uint32_t pos0 = n_pos0;
+                const int64_t off = n_off;
+                // a list longer than NPRE chunks: its further chunks first, as in the stored-rows loop below
+                const uint32_t w64x = w64 + NPRE * NT;
+                const bool hasx = w64x < len;
+                constexpr int NEX = 2;
+                uint4 ex[NEX];
+                float exs[NEX];
+                if (hasx) {
+#pragma unroll
+                    for (int e = 0; e < NEX; e++) {
+                        const int64_t idx = off + min(w64x + e * NT + lane, len - 1);
+                        ex[e] = codes4[idx];
+                        exs[e] = a.code_sums[idx];
+                    }
+                }
+                prefetch_meta(i + 1);
+                if (sel.dirty) {     // wave-uniform: publish this wave's bound on A, then take the workgroup's minimum
+                    if (lane == 0) atomicMin(wg_thr, f32_to_ordered(sel.thr_own));
+                    sel.dirty = false;
+                }
+                sel.refresh_with(*wg_thr);
+                if (hasx) {
+                    for (uint32_t jx = w64x; jx < len; jx += NEX * NT) {
+                        uint4 cur[NEX];
+                        float curs[NEX];
+#pragma unroll
+                        for (int e = 0; e < NEX; e++) { cur[e] = ex[e]; curs[e] = exs[e]; }
+                        if (jx + NEX * NT < len) {
+#pragma unroll
+                            for (int e = 0; e < NEX; e++) {
+                                const int64_t idx = off + min(jx + (NEX + e) * NT + lane, len - 1);
+                                ex[e] = codes4[idx];
+                                exs[e] = a.code_sums[idx];
+                            }
+                        }
+#pragma unroll
+                        for (int e = 0; e < NEX; e++) {
+                            const uint32_t j0e = jx + e * NT;
+                            if (j0e < len) {
+                                const float dis = adc16_halves<0>(cur[e], __fadd_rn(dis0, curs[e]), two);
+                                sel.offer_keyed(dis, pos0 + j0e + lane, j0e + lane < len);
+                            }
+                        }
+                    }
+                }
+                // the trips of the stored-rows loop: every load unconditional and in one place (see there)
+                auto trip = [&](auto cc_) {
+                    constexpr int C = decltype(cc_)::value;
+                    const uint32_t jc = w64 + C * NT;
+                    uint32_t g = jc < len ? 1u : 0u;      // (wave-uniform)
+                    float lo[8], hi[8];
+                    float dis = 0.f;
+                    if (g) {
+                        const uint4 cur = cr[C];
+                        { float (&v)[8] = lo; VLQ_G8LO_NW(0, cur.x, cur.y); }
+                        { float (&v)[8] = hi; VLQ_G8HI_NW(0, cur.z, cur.w); }
+                        dis = __fadd_rn(dis0, sr[C]);
+                    }
+                    load_chunk_s(cc_);
+                    g = __builtin_amdgcn_readfirstlane(g);
+                    asm volatile("" : "+s"(g));
+                    if (g) {
+                        VLQ_WAIT8(8, lo);
+#pragma unroll
+                        for (int m = 0; m < 8; m++) dis = __fadd_rn(dis, lo[m]);
+                        asm volatile("" : "+v"(dis));
+                        VLQ_WAIT8(0, hi);
+#pragma unroll
+                        for (int m = 0; m < 8; m++) dis = __fadd_rn(dis, hi[m]);
+                        sel.offer_keyed(dis, pos0 + jc + lane, jc + lane < len);
+                    }
+                };
+                trip(std::integral_constant<int, 0>{});
+                trip(std::integral_constant<int, 1>{});
+                if (NPRE == 3) trip(std::integral_constant<int, 2>{});
+                nscan += len;
+            }
+            if (t == 0) walk_state_finish(a, t_walk, i_end - i_begin, walk_mean);
+            walk_mean = -1;
+            // ---- end of the query: the waves' 64 best keys by (A, position), joined in wave 0 ----
+            sel.flush();
+            queue[wave * 64 + lane] = sel.best[0];
+            __syncthreads();
+            if (wave == 0) {
+                u64 b[1] = {sel.best[0]};
+                for (int w = 1; w < NW; w++) {      // the 64 smallest of both lists: bitonic split against the other reversed, merge
+                    b[0] = umin64(b[0], lane_reverse_u64(queue[w * 64 + lane]));
+                    wave_bitonic_merge<1>(b, lane);
+                }
+                const u64 kth = bcast_u64(b[0], a.k - 1);
+                // fewer than k codes: everything that was scanned is a finalist
+                const float T = kth == kMaxKey ? __builtin_inff()
+                                               : __fadd_rn(ordered_to_f32((uint32_t)(kth >> 32)), __fmul_rn(0.75f, sel.slack));    // 2.25 eps
+                const bool fin = b[0] != kMaxKey && ordered_to_f32((uint32_t)(b[0] >> 32)) <= T;
+                const u64 fmask = __ballot(fin);
+                // the 64th smallest retained key is itself within the bound: codes beyond the 64 kept (dropped from a full list,
+                // or more than 64 finalists) may belong to the result -- undecided, the stored-rows loop redoes the query
+                const bool und = (fmask >> 63) != 0;
+                if (!und) {
+                    u64 key = kMaxKey;
+                    if (fin) {
+                        // the reference's arithmetic for this code: fl(t2 + q) per entry, then dis0 + ... left to right
+                        const uint32_t pos = (uint32_t)b[0];
+                        int plo = 0, phi = a.nprobe;         // last probe p with cum[p] <= pos (emit_rows)
+                        while (phi - plo > 1) {
+                            const int mid = (plo + phi) >> 1;
+                            if (pm.cum[mid] <= pos) plo = mid; else phi = mid;
+                        }
+                        // (pm.pd0 is in walking order by now: the coarse distance by the probe's own index)
+                        float dis = a.coarse_dis[q * a.nprobe + plo];
+                        const uint4 cc = codes4[pm.poff[plo] + (int64_t)(pos - pm.cum[plo])];
+                        const float* row = a.term2 + (size_t)a.keys[q * a.nprobe + plo] * E;
+                        const uint32_t wds[4] = {cc.x, cc.y, cc.z, cc.w};
+                        float ent[16];
+#pragma unroll
+                        for (int m = 0; m < 16; m++) {
+                            const uint32_t c = (wds[m >> 2] >> (8 * (m & 3))) & 255u;
+                            ent[m] = __fadd_rn(row[m * 256 + c], lut[m * 256 + c]);
+                        }
+#pragma unroll
+                        for (int m = 0; m < 16; m++) dis = __fadd_rn(dis, ent[m]);
+                        key = make_key(dis, pos);
+                    }
+                    sel.best[0] = wave_sort64(key, lane);
+                    emit_rows<KPL>(sel, pm.cum, a, q, lane, [&](int p, int64_t& lkey, int64_t& loff) { lkey = a.keys[q * a.nprobe + p]; loff = pm.poff[p]; });
+                }
+                if (lane == 0) {
+                    sx[5] = und ? 1.f : 0.f;
+                    if (und) atomicAdd(a.sums_cnt, 1ull);
+                    else atomicAdd(a.sums_cnt + 1, (unsigned long long)__popcll(fmask));
+                }
+            }
+            __syncthreads();
+            if (sx[5] == 0.f) {      // decided: the rows are written
+                if (t == 0) atomicAdd(a.ncode, (unsigned long long)nscan);
+                if (badkey) *a.bad_key = 1;
+                return;
+            }
+        } else if (t == 0) {
+            atomicAdd(a.sums_cnt, 1ull);       // (not screened counts as undecided)
+        }
+        // undecided: the stored-rows loop below, from a fresh selection; this thread's part of the per-query table comes
+        // back from LDS (the slots it wrote and will overwrite with the first table)
+        sel.init(a.k, queue + wave * 64 * QR, lane);
+        if (t == 0) *wg_thr = f32_to_ordered(3.402823466e+38f);
+#pragma unroll
+        for (int i = 0; i < NI; i++) m2t3[i] = reinterpret_cast<const float4*>(lut)[i * NT + t];
+        nscan = 0;
+    }
     prefetch(i_begin);
     // (the first table build needs the row at once, so nothing is lost by waiting for the set-up's loads here -- and with
     // nothing pending on the way into the loop the compiler counts the loads younger than a row exactly: entering with the
@@ -272,7 +495,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((((KPL 
     // the chunk requested in the trip just finished)
     if (AHEAD) __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0)
     int buf = 0;
-    uint64_t nscan = 0;
     VLQ_PH(0);
     for (int i = i_begin; i < i_end; i++) {
         const uint32_t len = n_len;
@@ -797,8 +1019,18 @@ static void launch_scan16_t(const ScanArgs& a, const ScanLaunch& L, hipStream_t 
                            a, L.lut_region);
         return;
     }
-    if (L.imi) launch_scan16_i<KPL, NW, NBUF, PIPE, true>(a, L.lut_region, L.lds_bytes, s);
-    else launch_scan16_i<KPL, NW, NBUF, PIPE, false>(a, L.lut_region, L.lds_bytes, s);
+    if (L.imi) { launch_scan16_i<KPL, NW, NBUF, PIPE, true>(a, L.lut_region, L.lds_bytes, s); return; }
+    if constexpr (KPL == 1 && NBUF == 1 && !PIPE) {
+        // the same shape with the stored-sums loop (scan_plan.h: ScanPlan::code_sums decides; whole queries only).  The shape's
+        // name above stays the six arguments that select it; vlq_ivfpq_last_scan_info tells the two builds apart by rows=sums
+        if (a.code_sums && a.t2abs && a.sums_cnt && a.nsplit == 1 && a.tail_r == 0) {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(scan16_kernel<KPL, NW, NBUF, PIPE, false, false, true>), L.lds_bytes);
+            hipLaunchKernelGGL((scan16_kernel<KPL, NW, NBUF, PIPE, false, false, true>), dim3((unsigned)(8 * a.grid_per_xcd)), dim3(64 * NW),
+                               L.lds_bytes, s, a, L.lut_region);
+            return;
+        }
+    }
+    launch_scan16_i<KPL, NW, NBUF, PIPE, false>(a, L.lut_region, L.lds_bytes, s);
 }
 
 // the instantiation plan_scan chose (scan_plan.h: the shapes and what was measured for each)

@@ -29,6 +29,8 @@ struct ScanShape {
     int walk_first = -2;         // VLQ_WALK_FIRST
     int scan16_variant = -1;     // VLQ_SCAN16_VARIANT
     bool generic_scan = false;   // VLQ_GENERIC_SCAN
+    // the handle holds valid stored table sums, the switch is on and the handle has not dropped the loop (handle.h)
+    bool code_sums = false;
 };
 
 enum class ScanPath {
@@ -78,6 +80,7 @@ struct ScanPlan {
     int walk_seed_slots = 0;     // workgroups that share the chip, as the walk clock's seed model counts them
     int tail_slots = 0;          // ... as the split of the batch's tail counts them (scan16 paths)
     bool long_lists = false;     // ScanArgs::long_lists (0 on the fp16 path, which never set it)
+    bool code_sums = false;      // the launch takes scan16_kernel's stored-sums loop (ScanArgs::code_sums)
     ScanLaunch launch;
 };
 
@@ -85,7 +88,7 @@ struct ScanPlan {
 // dynamic LDS behind the table region (host mirror of the kernels' carve of smraw: scan16.hip around line 70 --
 // queue[nw][64 * qr] keys | ProbeMeta | misc (cut, nlive) | ord[nprobe] | wg_thr, 8-aligned | walk records; the same carve
 // in scan16h.hip, scanm.hip, and without wg_thr and the records in scan16_short_kernel / scanm_short.hip).  The 64 bytes
-// are slack for the alignments.  Each launcher requests exactly this; a change of the carve changes it here.
+// are slack for the alignments (scan16_kernel keeps the eight words of its stored-sums loop in them, behind wg_thr).  Each launcher requests exactly this; a change of the carve changes it here.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr size_t probe_meta_bytes(int nprobe) { return (size_t)nprobe * 24 + 8; }     // ProbeMeta (scan16_common.cuh)
 constexpr int kWalkRecordProbes = 64;    // up to here the kernels keep the probes' metadata once more, in walking order
@@ -101,6 +104,9 @@ constexpr size_t kTable16 = (size_t)4096 * 4;       // one [16][256] float table
 // ---------------------------------------------------------------------------------------------------------------------
 // the thresholds
 // ---------------------------------------------------------------------------------------------------------------------
+// The stored-sums loop of scan16_kernel (scan16.hip): the selection keeps 64 keys per wave and the end of the query takes at
+// most 64 finalists, so k stays well under that; built for the whole-query one-buffer shapes.
+constexpr int kSumsMaxK = 32;
 // list-length classes of an index (mean list length)
 constexpr int64_t kShortListCodes = 24;      // below: a few codes per list (the multi-index drivers) -- no table per probe pays
 constexpr int64_t kLongListCodes = 1024;     // from here: mean list >= 4 chunks of 256 codes
@@ -130,6 +136,10 @@ inline bool two_wave_batch(const ScanShape& s) { return s.ni >= kTwoWaveBatch; }
 constexpr int64_t kSlotsTwoWave = 2048, kSlotsOneBuffer = 1280, kSlotsFourWave = 1024;
 
 inline bool fast16(const ScanShape& s) { return s.table_mode == 1 && s.M == 16 && s.ksub == 256; }
+// an index whose pages plan_scan can route to the stored-sums loop: the handle builds the sums only for these
+inline bool scan_sums_index(const ScanShape& s) {
+    return fast16(s) && s.dsub == 8 && s.imi_nbits == 0 && !s.fp16_tables && s.scan_schedule <= 1 && !short_lists(s) && !long_lists(s);
+}
 
 // scan16_kernel's instantiation for a launch whose nsplit / tail_r / owned / imi are set in L
 inline void plan_scan16_shape(const ScanShape& s, ScanLaunch& L) {
@@ -314,6 +324,10 @@ inline ScanPlan plan_scan(const ScanShape& s) {
             p.path = ScanPath::scan16;
         }
         plan_scan16_shape(s, L);
+        // stored table sums instead of a table row per probe: whole queries on the one-buffer shapes, flat quantizer, the
+        // fused 8-wide sub-vectors, lists of a few hundred codes (the indexes scan_sums_index() lets the handle build sums for)
+        p.code_sums = s.code_sums && p.path == ScanPath::scan16 && s.k <= kSumsMaxK && L.kpl == 1 && L.nbuf == 1 && !L.pipe &&
+                      !L.imi && s.dsub == 8 && !longl;
         return p;
     }
     // table mode 0 on the engineered kernel: 8-, 16- and 32-byte codes, flat coarse quantizer, d <= 128 (a thread holds d

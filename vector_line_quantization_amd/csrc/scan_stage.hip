@@ -55,6 +55,60 @@ int ensure_term2(vlq_ivfpq_t h) {
     return VLQ_OK;
 }
 
+// what of a ScanShape the handle alone decides (the page and the call fill in the rest)
+static vlq::ScanShape index_shape(vlq_ivfpq_t h) {
+    vlq::ScanShape shape;
+    shape.M = h->M; shape.ksub = h->ksub; shape.dsub = h->dsub; shape.d = h->d; shape.nlist = h->nlist; shape.ntotal = h->ntotal;
+    shape.imi_nbits = h->imi_nbits; shape.table_mode = !h->by_residual ? 2 : (h->use_precomputed_table == 1 ? 1 : 0);
+    shape.fp16_tables = h->fp16_tables; shape.have_rank = h->have_rank;
+    shape.scan_schedule = h->scan_schedule; shape.max_codes = h->max_codes;
+    return shape;
+}
+
+// An index drops the stored-sums loop when more than kSumsDropNum / kSumsDropDen of the queries of the batches since the last
+// look were undecided.  An undecided query pays both loops, a decided one saves the difference: with t_rows and t_sums the
+// scan times of a batch on stored rows and on sums, the two cancel at the share s with s * t_sums = (1 - s) * (t_rows -
+// t_sums), s = 1 - t_sums / t_rows.  Measured on the headline shape (profiles/r07_scan_sums.txt): t_rows = 0.478 ms, t_sums =
+// 0.377 ms, s = 0.21; the constant is set at about half of that, 1 / 8, so that a handle near the break-even point does not stay on
+// the losing side because of a batch or two that were kinder than the rest.
+constexpr uint64_t kSumsDropNum = 1, kSumsDropDen = 8;
+
+void sums_defeated(vlq_ivfpq_t h) {
+    if (!h->sums_cnt_host || h->sums_dropped) return;
+    const uint64_t und = h->sums_cnt_host[0], dq = h->sums_q_copied - h->sums_q_base, du = und - h->sums_und_base;
+    if (dq == 0) return;
+    if (du * kSumsDropDen > dq * kSumsDropNum) h->sums_dropped = true;
+    h->sums_q_base = h->sums_q_copied;
+    h->sums_und_base = und;
+}
+
+// The stored table sums and the per-list magnitudes, for the indexes plan_scan can route to the loop (scan_sums_index).  Built
+// where the other one-time search costs are paid (api.hip: finish_index_build) and re-validated before a scan.  No memory for
+// the 4 bytes per slot, or no counters: false, and the search proceeds on stored rows -- same results, no error.
+bool ensure_code_sums(vlq_ivfpq_t h) {
+    if (h->scan_sums == 0 || h->sums_dropped || h->metric == 0 || h->polysemous_ht > 0 || h->ntotal <= 0) return false;
+    if (!vlq::scan_sums_index(index_shape(h)) || !h->term2_valid) return false;
+    if (h->sums_valid) return true;
+    std::string keep = err_slot();
+    auto quiet = [&](int rc) { if (rc != VLQ_OK) { (void)hipGetLastError(); err_slot() = keep; } return rc == VLQ_OK; };
+    if (!h->sums_cnt_host) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&h->sums_cnt_host), 16, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); h->sums_cnt_host = nullptr; return false;
+        }
+        h->sums_cnt_host[0] = h->sums_cnt_host[1] = 0;
+        if (!quiet(h->sums_cnt.reserve(16))) return false;
+        (void)hipMemsetAsync(h->sums_cnt.p, 0, 16, h->stream);
+    }
+    // one float per slot the code array holds (its capacity bounds every list's end)
+    if (!quiet(h->code_sums.reserve((h->codes.cap / (size_t)h->M + 1) * sizeof(float)))) return false;
+    if (!quiet(h->t2abs.reserve((size_t)h->nlist * sizeof(float)))) return false;
+    vlq::launch_code_sums(h->codes.as<uint8_t>(), h->list_off.as<int64_t>(), h->list_len.as<int64_t>(), h->nlist, h->term2.as<float>(),
+                          h->code_sums.as<float>(), h->t2abs.as<float>(), h->stream);
+    if (hipGetLastError() != hipSuccess) return false;
+    h->sums_valid = true;
+    return true;
+}
+
 // half(term 2) for the float16 tables (impl/IVFPQ.cu:599-684 toHalf).  As in the reference the entries must fit
 // the half range: byte-valued (SIFT-like) data has |term 2| up to 1e5 and would turn into infinities -- refused.
 static int ensure_term2h(vlq_ivfpq_t h) {
@@ -195,11 +249,12 @@ static int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t*
     if (h->imi_nbits > 0 && table_mode == 0)
         return fail(VLQ_ERR_UNSUPPORTED, "multi-index coarse quantizer without the precomputed table (type 2) is not built");
     const int64_t page = 32768;
-    vlq::ScanShape shape;
-    shape.M = h->M; shape.ksub = h->ksub; shape.dsub = h->dsub; shape.d = h->d; shape.nlist = h->nlist; shape.ntotal = h->ntotal;
-    shape.imi_nbits = h->imi_nbits; shape.table_mode = table_mode; shape.fp16_tables = h->fp16_tables; shape.have_rank = h->have_rank;
-    shape.scan_schedule = h->scan_schedule; shape.max_codes = h->max_codes;
+    vlq::ScanShape shape = index_shape(h);
     shape.n = n; shape.nprobe = nprobe; shape.k = k;
+    sums_defeated(h);
+    shape.code_sums = k <= vlq::kSumsMaxK && ensure_code_sums(h);
+    h->last_rows_sums = false;
+    bool sums_used = false;
     shape.walk_first = env.walk_first; shape.scan16_variant = env.scan16_variant; shape.generic_scan = env.generic_scan;
     for (int64_t i0 = 0; i0 < n; i0 += page) {
         const int64_t ni = std::min(page, n - i0);
@@ -223,6 +278,12 @@ static int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t*
         a.long_lists = plan.long_lists;
         a.nsplit = L.nsplit; a.tail_r = L.tail_r; a.tail_p = L.tail_p;
         a.xcd_chunk = L.xcd_chunk; a.grid_per_xcd = L.grid_per_xcd;
+        if (plan.code_sums) {
+            a.code_sums = h->code_sums.as<float>(); a.t2abs = h->t2abs.as<float>(); a.sums_cnt = h->sums_cnt.as<unsigned long long>();
+            h->sums_q_seen += (uint64_t)ni;
+            sums_used = true;
+        }
+        h->last_rows_sums = plan.code_sums;
         a.walk_first = plan.walk_first;
         a.walk_clock = env.walk_clock > 0 ? env.walk_clock : 0;
         if (env.walk_clock == 0 && a.walk_first >= 0) {
@@ -448,6 +509,10 @@ static int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t*
         }
     }
     HIP_TRY(hipGetLastError());
+    if (sums_used) {      // the undecided count reaches the host behind the batch; sums_defeated() looks at it before the next
+        HIP_TRY(hipMemcpyAsync(h->sums_cnt_host, h->sums_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
+        h->sums_q_copied = h->sums_q_seen;
+    }
     h->stat_nq += (uint64_t)n;
     h->order_hist_ready = false;
     return VLQ_OK;

@@ -110,6 +110,17 @@ __device__ __forceinline__ uint32_t wave_sort64_u32(uint32_t key, int lane) {
     return key;
 }
 
+// Maximum over the 64 lanes, in every lane (VALU only)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    v = max(v, lane_xor_u32(v, 32));
+    v = max(v, lane_xor_u32(v, 16));
+    v = max(v, lane_xor_u32(v, 8));
+    v = max(v, lane_xor_u32(v, 4));
+    v = max(v, lane_xor_u32(v, 2));
+    v = max(v, lane_xor_u32(v, 1));
+    return v;
+}
+
 // Inclusive prefix sum over the 64 lanes, VALU only (DPP row shifts, then the row totals by row_bcast:15 / :31).
 __device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);     // row_shr:1
@@ -264,6 +275,11 @@ struct WaveSelect {
     float thr_sh;     // nextup of the last shared minimum seen (+inf: none)
     float t_sh;       // the last shared minimum itself
     bool dirty;       // thr_own changed since the caller last published it
+    // Added to the k-th distance wherever it becomes a threshold (wave-uniform; -0 = none: x + -0 is x for every x).  A caller
+    // that selects on an APPROXIMATE distance sets it to more than twice the approximation's error bound: whatever is then
+    // rejected lies above the final k-th distance + slack, so every candidate within the bound of the exact top k is kept
+    // while the list has room (scan16.hip, the stored-sums loop).
+    float slack;
 
     __device__ __forceinline__ void init(int k_, u64* queue_, int lane_) {
 #pragma unroll
@@ -273,6 +289,7 @@ struct WaveSelect {
         t_sh = __builtin_inff();
         thr_sh = __builtin_inff();
         dirty = false;
+        slack = -0.0f;
         npend = 0;
         k = k_;
         lane = lane_;
@@ -293,7 +310,7 @@ struct WaveSelect {
         for (int r = 0; r < KPL; r++) best[r] = b.v[r];
         npend = 0;
         // (wave-uniform: keep it in a scalar register)
-        thr_own = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(b.kth)));
+        thr_own = __fadd_rn(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(b.kth))), slack);
         pos_own = __builtin_amdgcn_readfirstlane(b.kth_pos);
         thr = fminf(thr_own, thr_sh);
         thr_le = fminf(thr_own, t_sh);

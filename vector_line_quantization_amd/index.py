@@ -119,6 +119,16 @@ class GpuIVFPQ:
         check(lib().vlq_ivfpq_coarse_screen_state(self._h, C.byref(en), C.byref(rows), C.byref(und)))
         return bool(en.value), int(rows.value), int(und.value)
 
+    def set_scan_sums(self, mode):
+        """0 stored rows, 1 automatic (default): stored table sums in the 16-byte scan (speed and memory only; include/vlq_ivfpq.h)"""
+        check(lib().vlq_ivfpq_set_scan_sums(self._h, C.c_int(int(mode))))
+
+    def scan_sums_state(self):
+        """(enabled, queries scanned on sums, queries redone on stored rows, codes redone exactly)"""
+        en, seen, und, fin = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().vlq_ivfpq_scan_sums_state(self._h, C.byref(en), C.byref(seen), C.byref(und), C.byref(fin)))
+        return bool(en.value), int(seen.value), int(und.value), int(fin.value)
+
     def set_scan_schedule(self, mode):
         """0 automatic, 1 query-major, 2 list-owned (speed only; include/vlq_ivfpq.h)"""
         check(lib().vlq_ivfpq_set_scan_schedule(self._h, C.c_int(int(mode))))
