@@ -4,6 +4,7 @@
 //   "IxFI"  IndexFlatIP
 //   "IxF2"  IndexFlatL2            "Imiq"  MultiIndexQuantizer        "IvPQ"  IndexIVFPQ
 //   "IvFl"  IndexIVFFlat (index_io.cpp:276-283, :597-603)
+//   "IvSQ"  IndexIVFScalarQuantizer (index_io.cpp:208-215, :283-292, :439-447, :611-620)
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
 // and rejected.
@@ -16,6 +17,7 @@
 #include "IndexFlat.h"
 #include "IndexIVFPQ.h"
 #include "IndexPQ.h"
+#include "IndexScalarQuantizer.h"
 
 namespace faiss {
 
@@ -73,6 +75,15 @@ inline void read_pq(ProductQuantizer& pq, FILE* f) {
   rvec(f, pq.centroids);
 }
 
+inline void write_sq(const ScalarQuantizer& sq, FILE* f) {   // write_ScalarQuantizer, index_io.cpp:208-215
+  w1(f, sq.qtype); w1(f, sq.rangestat); w1(f, sq.rangestat_arg); w1(f, sq.d); w1(f, sq.code_size);
+  wvec(f, sq.trained);
+}
+inline void read_sq(ScalarQuantizer& sq, FILE* f) {          // read_ScalarQuantizer, index_io.cpp:439-447
+  r1(f, sq.qtype); r1(f, sq.rangestat); r1(f, sq.rangestat_arg); r1(f, sq.d); r1(f, sq.code_size);
+  rvec(f, sq.trained);
+}
+
 }  // namespace io_detail
 
 inline void write_index(const Index* idx, FILE* f) {
@@ -95,6 +106,18 @@ inline void write_index(const Index* idx, FILE* f) {
     w1(f, ivfl->maintain_direct_map);
     wvec(f, ivfl->direct_map);
     for (size_t i = 0; i < ivfl->nlist; i++) wvec(f, ivfl->vecs[i]);
+  } else if (const IndexIVFScalarQuantizer* ivsc = dynamic_cast<const IndexIVFScalarQuantizer*>(idx)) {
+    w1(f, fourcc("IvSQ"));                     // index_io.cpp:283-292
+    write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
+    w1(f, ivsc->nlist);
+    w1(f, ivsc->nprobe);
+    write_index(ivsc->quantizer, f);
+    for (size_t i = 0; i < ivsc->nlist; i++) wvec(f, ivsc->ids[i]);
+    w1(f, ivsc->maintain_direct_map);
+    wvec(f, ivsc->direct_map);
+    write_sq(ivsc->sq, f);
+    w1(f, ivsc->code_size);
+    for (size_t i = 0; i < ivsc->nlist; i++) wvec(f, ivsc->codes[i]);
   } else if (const IndexIVFPQ* ivpq = dynamic_cast<const IndexIVFPQ*>(idx)) {
     w1(f, fourcc("IvPQ"));
     write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
@@ -160,6 +183,27 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     for (size_t i = 0; i < iv->nlist; i++) {
       rvec(f, iv->vecs[i]);
       FAISS_THROW_IF_NOT(iv->vecs[i].size() == iv->ids[i].size() * (size_t)iv->d);
+    }
+    iv->lists_changed();
+    return iv.release();
+  }
+  if (h == fourcc("IvSQ")) {                   // index_io.cpp:611-620
+    std::unique_ptr<IndexIVFScalarQuantizer> iv(new IndexIVFScalarQuantizer());
+    read_header(iv.get(), f);                  // read_ivf_header, index_io.cpp:459-473
+    r1(f, iv->nlist);
+    r1(f, iv->nprobe);
+    iv->quantizer = read_index(f, precompute);
+    iv->own_fields = true;
+    iv->ids.resize(iv->nlist);
+    for (size_t i = 0; i < iv->nlist; i++) rvec(f, iv->ids[i]);
+    r1(f, iv->maintain_direct_map);
+    rvec(f, iv->direct_map);
+    read_sq(iv->sq, f);
+    r1(f, iv->code_size);
+    iv->codes.resize(iv->nlist);
+    for (size_t i = 0; i < iv->nlist; i++) {
+      rvec(f, iv->codes[i]);
+      FAISS_THROW_IF_NOT(iv->codes[i].size() == iv->ids[i].size() * iv->code_size);
     }
     iv->lists_changed();
     return iv.release();

@@ -407,6 +407,77 @@ int vlq_ivfflat_stats(vlq_ivfflat_t h, uint64_t* nq, uint64_t* nlist_visited, ui
  *   "kernel=scan_flat_kernel<1, L2> read=tile128 lds=40304".  Synchronises the stream. */
 int vlq_ivfflat_last_scan_info(vlq_ivfflat_t h, char* buf, int cap);
 
+/* ---- IVF scalar quantizer: inverted lists of 8- or 4-bit codes per component of the residual
+ * (faiss::IndexIVFScalarQuantizer, IndexScalarQuantizer.h:129-155, IndexScalarQuantizer.cpp:805-1002; what index_factory
+ * builds for "IVFx,SQ8" and "IVFx,SQ4").  A handle of its own, like the IVFFlat one: the coarse quantizer is the flat one of
+ * the IVFPQ handle (IndexFlatL2 for L2, IndexFlatIP for inner product), the lists hold rows of code_size bytes, and the scan
+ * (csrc/scan_sq.hip) decodes and accumulates in the reference's operation order, so D is bit-identical to
+ * search_with_probes_L2 / search_with_probes_ip (:884-956).
+ *   qtype      ScalarQuantizer::QuantizerType: 0 = QT_8bit, 1 = QT_4bit, 2 = QT_8bit_uniform, 3 = QT_4bit_uniform
+ *   code_size  d bytes at 8 bits, (d + 1) / 2 at 4 bits: component i is the low nibble of byte i / 2 for even i, the high one
+ *              for odd i (:85-93)
+ *   trained    ScalarQuantizer::trained: vmin[d], vdiff[d]; the uniform types hold two floats (:270-286, :369-392)
+ *   decode     rec_i = vmin_i + ((c + 0.5f) * (1.f / den)) * vdiff_i when d % 8 == 0 (the AVX path, :67-80, :96-115, :545-549),
+ *              rec_i = vmin_i + ((c + 0.5f) / den) * vdiff_i otherwise (:63-65, :91-93, :538-542); den = 255 or 15; nothing fused
+ *   L2         y = x - centroid of the probe; t_i = (y_i - rec_i)^2; d % 8 == 0: eight accumulators over i mod 8, joined as
+ *              ((a0+a1)+(a2+a3)) + ((a4+a5)+(a6+a7)) (:153-172); otherwise one accumulator from 0 (:134-146)
+ *   inner product  y = x; t_i = y_i * rec_i; accu0 = the probe's coarse inner product; d % 8 == 0: eight accumulators from
+ *              0, (accu0 + ((a0+a1)+(a2+a3))) + ((a4+a5)+(a6+a7)) (:205-224); otherwise one accumulator from accu0 (:187-198)
+ *   rows       L2 ascending, padding FLT_MAX / -1 (max-heap, dis < top, :948); inner product descending, padding
+ *              -FLT_MAX / -1 (min-heap, ip > top, :909).  An equal value never replaces an earlier one of the scan order.
+ * A key < 0 ENDS the walk of that query's probes (break, :897, :934) -- the IVFFlat scan skips such a key and goes on.  The
+ * reference does not check key >= nlist; here it raises the bad-key flag: VLQ_ERR_INVALID from the search call with a host D
+ * or I, from the next vlq_ivfsq_last_scan_info() otherwise.  There is no max_codes and no stats struct in the reference.
+ * vdiff_i == 0 (a constant dimension of the training residuals) makes the reference's encoder divide by zero; that result is
+ * not pinned: vlq_ivfsq_set_trained refuses such a range with VLQ_ERR_INVALID.
+ * Limits: k <= VLQ_MAX_K, nprobe <= VLQ_MAX_NPROBE, 16 * d + 24 * nprobe within the kernel's LDS (d up to 7 804 with few probes):
+ * VLQ_ERR_UNSUPPORTED otherwise, there is no other path.  Only RS_minmax training is stated (vlq.GpuIVFSQ.train, on the host);
+ * the non-IVF IndexScalarQuantizer is not built.  Pointers marked [h|d] as above. */
+typedef struct vlq_ivfsq_s* vlq_ivfsq_t;
+
+/* IndexIVFScalarQuantizer::IndexIVFScalarQuantizer (:809-818).  metric: 0 = inner product, 1 = L2. */
+int vlq_ivfsq_create(vlq_ivfsq_t* out, int device, int d, int nlist, int qtype, int metric);
+void vlq_ivfsq_destroy(vlq_ivfsq_t h);
+int vlq_ivfsq_set_stream(vlq_ivfsq_t h, void* hip_stream);
+/* the trained quantizer: centroids[nlist*d] [h|d] */
+int vlq_ivfsq_set_coarse_centroids(vlq_ivfsq_t h, const float* centroids);
+/* ScalarQuantizer::trained (what sq.train leaves, :588-603): host floats, count = 2 * d (2 for the uniform types).
+ * A vdiff that is zero, negative or not finite: VLQ_ERR_INVALID.  get_trained: out[count] host floats. */
+int vlq_ivfsq_set_trained(vlq_ivfsq_t h, const float* trained, int count);
+int vlq_ivfsq_get_trained(vlq_ivfsq_t h, float* out, int count);
+int vlq_ivfsq_code_size(vlq_ivfsq_t h);
+/* IndexIVFScalarQuantizer::codes / IndexIVF::ids, list-contiguous: codes[ntotal*code_size], ids[ntotal],
+ * list_offsets[nlist+1] [h|d].  Replaces the lists. */
+int vlq_ivfsq_set_lists(vlq_ivfsq_t h, const uint8_t* codes, const int64_t* ids, const int64_t* list_offsets);
+/* IndexIVFScalarQuantizer::add_with_ids (:842-881): quantizer->assign (1-NN), residual, encode_vector (:446-455, :520-529:
+ * (r_i - vmin_i) / vdiff_i clamped to [0, 1]; (int)(255 * xi) in float at 8 bits, (int)(xi * 15.0) in double at 4 bits), append
+ * in input order; the id of vector i is xids ? xids[i] : ntotal + i.  x[n*d], xids[n] [h|d] or NULL. */
+int vlq_ivfsq_add(vlq_ivfsq_t h, int64_t n, const float* x, const int64_t* xids);
+/* the same with a given assignment instead of quantizer->assign: a list id < 0 or >= nlist drops the vector (:862) */
+int vlq_ivfsq_add_preassigned(vlq_ivfsq_t h, int64_t n, const float* x, const int64_t* xids, const int64_t* assign);
+/* the codes add would store, nothing stored: codes[n*code_size] [h|d]; assign_out[n] [h|d] or NULL */
+int vlq_ivfsq_encode(vlq_ivfsq_t h, int64_t n, const float* x, uint8_t* codes, int64_t* assign_out);
+int vlq_ivfsq_reserve_memory(vlq_ivfsq_t h, int64_t num_vecs);
+int vlq_ivfsq_reclaim_memory(vlq_ivfsq_t h, uint64_t* bytes_reclaimed);
+int64_t vlq_ivfsq_ntotal(vlq_ivfsq_t h);
+/* codes_out[len*code_size], ids_out[len] host buffers (either may be NULL) */
+int vlq_ivfsq_list_length(vlq_ivfsq_t h, int list_id, int64_t* len);
+int vlq_ivfsq_get_list(vlq_ivfsq_t h, int list_id, uint8_t* codes_out, int64_t* ids_out);
+/* IndexIVF::reset: every list emptied, ntotal = 0; the quantizers stay */
+int vlq_ivfsq_reset(vlq_ivfsq_t h);
+/* quantizer->search(n, x, nprobe) (:968): cdis / keys [n*nprobe] [h|d] */
+int vlq_ivfsq_coarse_search(vlq_ivfsq_t h, int64_t n, const float* x, int nprobe, float* cdis, int64_t* keys);
+/* IndexIVFScalarQuantizer::search (:959-989).  x, D, I [h|d]. */
+int vlq_ivfsq_search(vlq_ivfsq_t h, int64_t n, const float* x, int nprobe, int k, float* D, int64_t* I);
+/* search_with_probes_L2 / search_with_probes_ip (:884-956) from given probes: keys[n*nprobe] [h|d]; coarse_dis[n*nprobe]
+ * [h|d] is read under inner product only (accu0, :898) and may be NULL for L2 */
+int vlq_ivfsq_search_preassigned(vlq_ivfsq_t h, int64_t n, const float* x, const int64_t* keys, const float* coarse_dis,
+                                 int nprobe, int k, float* D, int64_t* I);
+/* Introspection, speed only: the kernel instantiation and read path of the last scan, as text:
+ *   "kernel=scan_sq_kernel<1, L2, 8, nonuniform, order8> read=tile128 lds=41760".  Synchronises the stream; raises a
+ * pending bad-key error. */
+int vlq_ivfsq_last_scan_info(vlq_ivfsq_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,11 @@ SYMBOLS = [
     "vlq_ivfflat_reclaim_memory", "vlq_ivfflat_ntotal", "vlq_ivfflat_list_length", "vlq_ivfflat_get_list", "vlq_ivfflat_reset",
     "vlq_ivfflat_coarse_search", "vlq_ivfflat_search", "vlq_ivfflat_search_preassigned", "vlq_ivfflat_stats",
     "vlq_ivfflat_last_scan_info",
+    # IVF scalar quantizer (vlq_ivfsq_t)
+    "vlq_ivfsq_create", "vlq_ivfsq_destroy", "vlq_ivfsq_set_stream", "vlq_ivfsq_set_coarse_centroids", "vlq_ivfsq_set_trained",
+    "vlq_ivfsq_get_trained", "vlq_ivfsq_code_size", "vlq_ivfsq_set_lists", "vlq_ivfsq_add", "vlq_ivfsq_add_preassigned", "vlq_ivfsq_encode",
+    "vlq_ivfsq_reserve_memory", "vlq_ivfsq_reclaim_memory", "vlq_ivfsq_ntotal", "vlq_ivfsq_list_length", "vlq_ivfsq_get_list",
+    "vlq_ivfsq_reset", "vlq_ivfsq_coarse_search", "vlq_ivfsq_search", "vlq_ivfsq_search_preassigned", "vlq_ivfsq_last_scan_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -94,6 +99,8 @@ def lib():
         L.vlq_ivfpq_destroy.restype = None
         L.vlq_ivfflat_ntotal.restype = C.c_int64
         L.vlq_ivfflat_destroy.restype = None
+        L.vlq_ivfsq_ntotal.restype = C.c_int64
+        L.vlq_ivfsq_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

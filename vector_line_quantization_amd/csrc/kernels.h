@@ -315,6 +315,18 @@ void launch_coarse_ip_finish(float* cdis, const int64_t* keys, int64_t n, hipStr
 // Which instantiation, read path and LDS size serve a shape is plan_flat_scan's decision (flat_plan.h); false: not built.
 bool launch_scan_flat(const ScanArgs& a, bool inner_product, unsigned long long* nlist_visited, hipStream_t s);
 
+// IVF scalar quantizer (IndexIVFScalarQuantizer::search, IndexScalarQuantizer.cpp:884-989; scan_sq.hip): a.codes holds the lists'
+// codes as rows of sq_code_size(d, qtype) bytes; a.queries, a.coarse (the centroids: the L2 residual of every probe), a.keys,
+// a.coarse_dis (inner product only: accu0), a.ids, a.list_off / a.list_len, a.D / a.I, a.bad_key, a.nq, a.nprobe, a.k, a.d,
+// a.nlist are read, nothing else.  trained: ScalarQuantizer::trained on the device (vmin[d], vdiff[d]; two floats for the
+// uniform types).  Which instantiation, read path and LDS size serve a shape is plan_sq_scan's decision (sq_plan.h); false: not
+// built.
+bool launch_scan_sq(const ScanArgs& a, int qtype, bool inner_product, const float* trained, hipStream_t s);
+// ScalarQuantizer encode_vector of the residuals x[i] - coarse[assign[i]] (IndexScalarQuantizer.cpp:446-455, :520-529, :869-876):
+// codes[n][code_size]; a vector whose assign is outside 0 .. nlist-1 gets zero bytes
+void launch_sq_encode(const float* x, int64_t n, int d, const float* coarse, const int64_t* assign, int nlist, const float* trained,
+                      int qtype, uint8_t* codes, hipStream_t s);
+
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this
 inline size_t query_order_bins_padded(int nlist) {

@@ -487,6 +487,179 @@ class GpuIVFFlat:
         return buf.value.decode()
 
 
+class GpuIVFSQ:
+    """faiss::IndexIVFScalarQuantizer (IndexScalarQuantizer.h:129-155; "IVFx,SQ8" / "IVFx,SQ4" of index_factory): inverted
+    lists of 8- or 4-bit codes per component of the residual.  qtype: "8bit", "4bit", "8bit_uniform", "4bit_uniform" (or
+    ScalarQuantizer::QuantizerType's number).  metric "l2": ascending distances, FLT_MAX / -1 padding; "ip": descending inner
+    products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfsq_*)."""
+
+    METRICS = GpuIVFPQ.METRICS
+    QTYPES = {"8bit": 0, "4bit": 1, "8bit_uniform": 2, "4bit_uniform": 3}      # ScalarQuantizer::QuantizerType
+
+    def __init__(self, d, nlist, qtype, device=0, metric="l2"):
+        self.d, self.nlist, self.device = d, nlist, device
+        self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        qt = self.QTYPES.get(qtype, qtype)
+        if qt not in self.QTYPES.values():
+            raise ValueError("qtype %r (one of %s)" % (qtype, ", ".join(repr(s) for s in self.QTYPES)))
+        self.metric, self.qtype = metric, int(qt)
+        self.uniform = self.qtype >= 2
+        self.bits = 8 if self.qtype in (0, 2) else 4
+        check(lib().vlq_ivfsq_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist), C.c_int(self.qtype),
+                                     C.c_int(self.METRICS[metric])))
+        self.code_size = int(lib().vlq_ivfsq_code_size(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_ivfsq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    _out = GpuIVFPQ._out
+
+    # --- state ------------------------------------------------------------
+    def set_stream(self, stream_ptr):
+        check(lib().vlq_ivfsq_set_stream(self._h, C.c_void_p(stream_ptr or 0)))
+
+    def set_coarse_centroids(self, c):
+        p, _k = _ptr(c, np.float32)
+        check(lib().vlq_ivfsq_set_coarse_centroids(self._h, p))
+        # train() takes the residuals on the host
+        host = c.detach().cpu().numpy() if _is_torch(c) else c
+        self._centroids = np.array(host, dtype=np.float32).reshape(self.nlist, self.d)
+
+    def set_trained(self, trained):
+        """ScalarQuantizer::trained: vmin[d] then vdiff[d] (two floats for the uniform types), host floats"""
+        t = np.ascontiguousarray(np.asarray(trained, dtype=np.float32).ravel())
+        check(lib().vlq_ivfsq_set_trained(self._h, t.ctypes.data_as(C.c_void_p), C.c_int(t.size)))
+
+    @property
+    def trained(self):
+        t = np.empty(2 if self.uniform else 2 * self.d, np.float32)
+        check(lib().vlq_ivfsq_get_trained(self._h, t.ctypes.data_as(C.c_void_p), C.c_int(t.size)))
+        return t
+
+    def train(self, x):
+        """IndexIVFScalarQuantizer::train_residual with the constructor's RS_minmax, rangestat_arg 0
+        (IndexScalarQuantizer.cpp:824-839, :270-286, :369-392): the 1-NN assignment runs on the device, the residuals and their
+        minima / maxima are taken in float32 on the host."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        _cd, keys = self.coarse_search(x, 1)
+        if (keys < 0).any():
+            raise ValueError("a training vector has no nearest centroid")
+        cent = self._centroids
+        res = x - cent[keys[:, 0]]
+        if self.uniform:
+            vmin, vmax = res.min(), res.max()
+        else:
+            vmin, vmax = res.min(axis=0), res.max(axis=0)
+        self.set_trained(np.concatenate([np.atleast_1d(vmin), np.atleast_1d((vmax - vmin).astype(np.float32))]))
+
+    def set_lists(self, codes, ids, list_offsets):
+        """codes [ntotal][code_size] uint8 and ids [ntotal] in list-contiguous order, list_offsets [nlist + 1]"""
+        pv, _a = _ptr(codes, np.uint8)
+        pi, _b = _ptr(ids, np.int64)
+        po, _c = _ptr(list_offsets, np.int64)
+        check(lib().vlq_ivfsq_set_lists(self._h, pv, pi, po))
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_ivfsq_ntotal(self._h))
+
+    def list_length(self, i):
+        n = C.c_int64()
+        check(lib().vlq_ivfsq_list_length(self._h, C.c_int(i), C.byref(n)))
+        return n.value
+
+    def get_list(self, i):
+        n = self.list_length(i)
+        codes = np.empty((n, self.code_size), np.uint8)
+        ids = np.empty((n,), np.int64)
+        check(lib().vlq_ivfsq_get_list(self._h, C.c_int(i), codes.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        return codes, ids
+
+    def reset(self):
+        check(lib().vlq_ivfsq_reset(self._h))
+
+    # --- add --------------------------------------------------------------
+    def add(self, x, xids=None):
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        check(lib().vlq_ivfsq_add(self._h, C.c_int64(x.shape[0]), px, pi))
+
+    def add_preassigned(self, x, assign, xids=None):
+        """add_with_ids behind a given assignment: a negative list id drops the vector"""
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        pa, _c = _ptr(assign, np.int64)
+        check(lib().vlq_ivfsq_add_preassigned(self._h, C.c_int64(x.shape[0]), px, pi, pa))
+
+    def encode(self, x):
+        """(codes [n][code_size], assignment [n]) that add would store; nothing is stored"""
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        codes = np.empty((n, self.code_size), np.uint8)
+        assign = np.empty((n,), np.int64)
+        check(lib().vlq_ivfsq_encode(self._h, C.c_int64(n), px, codes.ctypes.data_as(C.c_void_p), assign.ctypes.data_as(C.c_void_p)))
+        return codes, assign
+
+    def reserve_memory(self, num_vecs):
+        check(lib().vlq_ivfsq_reserve_memory(self._h, C.c_int64(num_vecs)))
+
+    def reclaim_memory(self):
+        n = C.c_uint64()
+        check(lib().vlq_ivfsq_reclaim_memory(self._h, C.byref(n)))
+        return n.value
+
+    # --- search -----------------------------------------------------------
+    def search(self, x, nprobe, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _b = _out_ptr(D, np.float32)
+        pI, _c = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfsq_search(self._h, C.c_int64(n), px, C.c_int(nprobe), C.c_int(k), pD, pI))
+        return D, I
+
+    def search_preassigned(self, x, keys, coarse_dis, k, D=None, I=None):
+        """coarse_dis [n][nprobe] is read under inner product only and may be None for L2"""
+        n, nprobe = x.shape[0], keys.shape[1]
+        px, _a = _ptr(x, np.float32)
+        pk, _b = _ptr(keys, np.int64)
+        pc, _f = _ptr(coarse_dis, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        pD, _d = _out_ptr(D, np.float32)
+        pI, _e = _out_ptr(I, np.int64)
+        check(lib().vlq_ivfsq_search_preassigned(self._h, C.c_int64(n), px, pk, pc, C.c_int(nprobe), C.c_int(k), pD, pI))
+        return D, I
+
+    def coarse_search(self, x, nprobe, cdis=None, keys=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        cdis = self._out(cdis, (n, nprobe), np.float32, x)
+        keys = self._out(keys, (n, nprobe), np.int64, x)
+        pc, _b = _out_ptr(cdis, np.float32)
+        pk, _c = _out_ptr(keys, np.int64)
+        check(lib().vlq_ivfsq_coarse_search(self._h, C.c_int64(n), px, C.c_int(nprobe), pc, pk))
+        return cdis, keys
+
+    # --- introspection ----------------------------------------------------
+    def last_scan_info(self):
+        """the kernel instantiation and read path of the last list scan (include/vlq_ivfpq.h); raises a pending bad-key error"""
+        buf = C.create_string_buffer(256)
+        check(lib().vlq_ivfsq_last_scan_info(self._h, buf, C.c_int(256)))
+        return buf.value.decode()
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
