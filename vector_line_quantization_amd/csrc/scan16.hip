@@ -157,7 +157,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SUMS &
     const bool badkey = probe_meta_fill(a, q, pm, t, NT);
     VLQ_PH(9);
     float4 m2t3[NI];
-    load_query_table16<NI>(a, q, t, lane, wave, m2t3);
+    if (!SUMS) load_query_table16<NI>(a, q, t, lane, wave, m2t3);
     // The stored-sums loop (scan_sum_bound.h): the per-query table -2 <x_m, .> goes to LDS ONCE and serves
     // every probe; a code's distance is approximated by A = (dis0 + code_sums[slot]) + its 16 table entries, the selection runs
     // on A, and only the few codes within the error bound of the k-th A are redone in the reference's arithmetic at the end.
@@ -167,15 +167,33 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SUMS &
     if (sums_on) {
         // sum_m max_c |q[m][c]|: float4 i of this wave belongs to sub-quantizer NW * i + wave; the bit pattern of |x| orders
         // like the value and carries a NaN to the top
+        // The table is produced two float4 at a time and each pair stored before the next is requested (the loads may not
+        // cross the marker): a float4 takes ten 16-byte codebook and query loads, and with all of the two-wave shape's eight
+        // requested at once the build spilled 24 VGPRs here -- 72 MB written and read back per launch of the headline batch
+        // (profiles/r08_scan_dense.txt: 0.4382 -> 0.4306 ms per step, WRITE_SIZE 75.8 -> 2.2 MB).  m2t3 is dead behind this
+        // block: the stored-rows fallback reads its part back from LDS.
+        constexpr int QG = 2;
+        static_assert(NI % QG == 0 && NI / QG <= 4, "groups of the per-query table");
         float qs = 0.f;
+        auto group = [&](auto g_) {
+            constexpr int I0 = decltype(g_)::value * QG;
+            if constexpr (I0 < NI) {
+                asm volatile("" ::: "memory");
+                load_query_table16_range<NI, I0, I0 + QG>(a, q, t, lane, wave, m2t3);
 #pragma unroll
-        for (int i = 0; i < NI; i++) {
-            reinterpret_cast<float4*>(lut)[i * NT + t] = m2t3[i];
-            uint32_t v = max(max(__float_as_uint(m2t3[i].x) & 0x7fffffffu, __float_as_uint(m2t3[i].y) & 0x7fffffffu),
-                             max(__float_as_uint(m2t3[i].z) & 0x7fffffffu, __float_as_uint(m2t3[i].w) & 0x7fffffffu));
-            v = wave_max_u32(v);
-            qs = scan_sum_up(__fadd_rn(qs, __uint_as_float(v)));
-        }
+                for (int i = I0; i < I0 + QG; i++) {
+                    reinterpret_cast<float4*>(lut)[i * NT + t] = m2t3[i];
+                    uint32_t v = max(max(__float_as_uint(m2t3[i].x) & 0x7fffffffu, __float_as_uint(m2t3[i].y) & 0x7fffffffu),
+                                     max(__float_as_uint(m2t3[i].z) & 0x7fffffffu, __float_as_uint(m2t3[i].w) & 0x7fffffffu));
+                    v = wave_max_u32(v);
+                    qs = scan_sum_up(__fadd_rn(qs, __uint_as_float(v)));
+                }
+            }
+        };
+        group(std::integral_constant<int, 0>{});
+        group(std::integral_constant<int, 1>{});
+        group(std::integral_constant<int, 2>{});
+        group(std::integral_constant<int, 3>{});
         if (lane == 0) sx[1 + wave] = qs;
     }
     WalkPre wpre;
@@ -321,83 +339,92 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SUMS &
             sel.slack = __fmul_rn(3.f, eps);
             float sr[3] = {0.f, 0.f, 0.f};
             const uint4* codes4 = reinterpret_cast<const uint4*>(a.codes);
-            // this thread's code of trip c of the prefetched list and the code's stored sum (same slot), clamped
-            auto load_chunk_s = [&](auto cc_) {
-                constexpr int C = decltype(cc_)::value;
-                const int64_t idx = n_off + min((uint32_t)t + C * NT, n_len - 1);
-                cr[C] = codes4[idx];
-                sr[C] = a.code_sums[idx];
-            };
-            prefetch_meta(i_begin);
-            if (i_begin < nlive) {
-                load_chunk_s(std::integral_constant<int, 0>{});
-                load_chunk_s(std::integral_constant<int, 1>{});
-                if (NPRE == 3) load_chunk_s(std::integral_constant<int, 2>{});
-            }
-            const uint32_t w64 = (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 64;
-            for (int i = i_begin; i < i_end; i++) {      // no row, no table build, no workgroup barrier
-                const uint32_t len = n_len;
-                const float dis0 = n_dis0;
-                const uint32_t pos0 = n_pos0;
-                const int64_t off = n_off;
-                // a list longer than NPRE chunks: its further chunks first, as in the stored-rows loop below
-                const uint32_t w64x = w64 + NPRE * NT;
-                const bool hasx = w64x < len;
-                constexpr int NEX = 2;
-                uint4 ex[NEX];
-                float exs[NEX];
-                if (hasx) {
-#pragma unroll
-                    for (int e = 0; e < NEX; e++) {
-                        const int64_t idx = off + min(w64x + e * NT + lane, len - 1);
-                        ex[e] = codes4[idx];
-                        exs[e] = a.code_sums[idx];
+            // The dense stream: the live probes' codes, in walking order, are one index space [0, total)
+            // of sum(len) codes; wave w takes its 64-blocks b = w, w + NW, ... -- every trip full but the last, loads NPRE blocks
+            // ahead across list boundaries.  A code needs its slot (f + adelta), its position (f + pdelta) and its probe's dis0;
+            // lane i of every wave keeps probe i's running end We and these three in registers (up to 64 probes at a time: a
+            // longer walk is streamed in windows of 64 probes), and a wave-uniform cursor steps through them with v_readlane --
+            // no LDS round trip behind the gathers, nothing per lane unless the block holds a list boundary.
+            const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+            for (int w0 = i_begin; w0 < i_end; w0 += 64) {
+                uint32_t r_len = 0, r_pos = 0;
+                float r_d0 = 0.f;
+                int64_t r_off = 0;
+                if (w0 + lane < i_end) {
+                    if (recs) {
+                        r_len = pm.plen[w0 + lane]; r_pos = w_pos[w0 + lane]; r_d0 = pm.pd0[w0 + lane]; r_off = w_off[w0 + lane];
+                    } else {
+                        const int p = ord[w0 + lane];
+                        r_len = pm.plen[p]; r_pos = pm.cum[p]; r_d0 = pm.pd0[p]; r_off = pm.poff[p];
                     }
                 }
-                prefetch_meta(i + 1);
-                if (sel.dirty) {     // wave-uniform: publish this wave's bound on A, then take the workgroup's minimum
-                    if (lane == 0) atomicMin(wg_thr, f32_to_ordered(sel.thr_own));
-                    sel.dirty = false;
-                }
-                sel.refresh_with(*wg_thr);
-                if (hasx) {
-                    for (uint32_t jx = w64x; jx < len; jx += NEX * NT) {
-                        uint4 cur[NEX];
-                        float curs[NEX];
-#pragma unroll
-                        for (int e = 0; e < NEX; e++) { cur[e] = ex[e]; curs[e] = exs[e]; }
-                        if (jx + NEX * NT < len) {
-#pragma unroll
-                            for (int e = 0; e < NEX; e++) {
-                                const int64_t idx = off + min(jx + (NEX + e) * NT + lane, len - 1);
-                                ex[e] = codes4[idx];
-                                exs[e] = a.code_sums[idx];
-                            }
-                        }
-#pragma unroll
-                        for (int e = 0; e < NEX; e++) {
-                            const uint32_t j0e = jx + e * NT;
-                            if (j0e < len) {
-                                const float dis = adc16_halves<0>(cur[e], __fadd_rn(dis0, curs[e]), two);
-                                sel.offer_keyed(dis, pos0 + j0e + lane, j0e + lane < len);
-                            }
-                        }
+                const uint32_t r_we = wave_scan_incl_u32(r_len);       // (positions are 32 bits: so is the sum)
+                r_off -= (int64_t)(r_we - r_len);                      // slot = f + adelta
+                r_pos -= r_we - r_len;                                 // position = f + pdelta (mod 2^32)
+                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)r_we, 63);
+                nscan += total;
+                if (total == 0) continue;
+                const uint32_t nblk = (total + 63) >> 6, last = total - 1;
+                // the cursor: probe ci of the window covers [c_w, c_we) of the stream
+                int ci = -1;
+                uint32_t c_w = 0, c_we = 0, c_pd = 0;
+                float c_d0 = 0.f;
+                int64_t c_ad = 0;
+                auto step = [&]() {
+                    ci = __builtin_amdgcn_readfirstlane(ci + 1);
+                    c_w = c_we;
+                    c_we = (uint32_t)__builtin_amdgcn_readlane((int)r_we, ci);
+                    c_pd = (uint32_t)__builtin_amdgcn_readlane((int)r_pos, ci);
+                    c_d0 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(r_d0), ci));
+                    c_ad = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)r_off >> 32), ci) << 32) |
+                                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)r_off, ci));
+                };
+                // slot, position and dis0 of this lane's code of block b.  Flat indices are clamped to the last code (a block
+                // behind the end is requested like any other -- every load unconditional -- and never consumed), so the cursor
+                // stops at the last probe (We = total > last) and every slot lies inside a visited list.  Any number of
+                // boundaries in one block, empty probes included: a lane takes the values of the last probe that starts at or
+                // before its index.
+                auto resolve = [&](uint32_t b, int64_t& idx, uint32_t& pos, float& d0) {
+                    const uint32_t f0 = b * 64u;
+                    const uint32_t f0c = min(f0, last), fmax = min(f0 + 63u, last);
+                    while (f0c >= c_we) step();
+                    const uint32_t fc = min(f0 + (uint32_t)lane, last);
+                    idx = (int64_t)fc + c_ad;
+                    pos = fc + c_pd;
+                    d0 = c_d0;
+                    while (fmax >= c_we) {
+                        step();
+                        if (fc >= c_w) { idx = (int64_t)fc + c_ad; pos = fc + c_pd; d0 = c_d0; }
                     }
-                }
-                // the trips of the stored-rows loop: every load unconditional and in one place (see there)
-                auto trip = [&](auto cc_) {
+                };
+                uint32_t ps[3] = {0, 0, 0};
+                float ds[3] = {0.f, 0.f, 0.f};
+                // this wave's block of slot C and the block's stored sums; the slot's position and dis0 travel with it
+                auto load_block = [&](auto cc_, uint32_t b) {
                     constexpr int C = decltype(cc_)::value;
-                    const uint32_t jc = w64 + C * NT;
-                    uint32_t g = jc < len ? 1u : 0u;      // (wave-uniform)
+                    int64_t idx;
+                    resolve(b, idx, ps[C], ds[C]);
+                    cr[C] = codes4[idx];
+                    sr[C] = a.code_sums[idx];
+                };
+                load_block(std::integral_constant<int, 0>{}, wv);
+                load_block(std::integral_constant<int, 1>{}, wv + NW);
+                if (NPRE == 3) load_block(std::integral_constant<int, 2>{}, wv + 2 * NW);
+                // the trips of the stored-rows loop: every load unconditional and in one place (see there)
+                auto trip = [&](auto cc_, uint32_t bc) {
+                    constexpr int C = decltype(cc_)::value;
+                    uint32_t g = bc < nblk ? 1u : 0u;      // (wave-uniform)
                     float lo[8], hi[8];
                     float dis = 0.f;
+                    const uint32_t pos = ps[C];
                     if (g) {
                         const uint4 cur = cr[C];
                         { float (&v)[8] = lo; VLQ_G8LO_NW(0, cur.x, cur.y); }
                         { float (&v)[8] = hi; VLQ_G8HI_NW(0, cur.z, cur.w); }
-                        dis = __fadd_rn(dis0, sr[C]);
+                        dis = __fadd_rn(ds[C], sr[C]);
+                        asm volatile("" : "+v"(dis));      // (the sum's register is free before it is requested again)
                     }
-                    load_chunk_s(cc_);
+                    load_block(cc_, bc + NPRE * NW);
                     g = __builtin_amdgcn_readfirstlane(g);
                     asm volatile("" : "+s"(g));
                     if (g) {
@@ -408,13 +435,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((SUMS &
                         VLQ_WAIT8(0, hi);
 #pragma unroll
                         for (int m = 0; m < 8; m++) dis = __fadd_rn(dis, hi[m]);
-                        sel.offer_keyed(dis, pos0 + jc + lane, jc + lane < len);
+                        sel.offer_keyed(dis, pos, bc * 64u + (uint32_t)lane < total);
                     }
                 };
-                trip(std::integral_constant<int, 0>{});
-                trip(std::integral_constant<int, 1>{});
-                if (NPRE == 3) trip(std::integral_constant<int, 2>{});
-                nscan += len;
+                for (uint32_t b = wv; b < nblk; b += NPRE * NW) {
+                    // (once per NPRE blocks; the cadence only decides how stale the shared bound may be: a stale one admits more)
+                    if (sel.dirty) {     // wave-uniform: publish this wave's bound on A, then take the workgroup's minimum
+                        if (lane == 0) atomicMin(wg_thr, f32_to_ordered(sel.thr_own));
+                        sel.dirty = false;
+                    }
+                    sel.refresh_with(*wg_thr);
+                    // (the shared word has arrived before the first gather is issued: its wait would otherwise land behind the
+                    // sixteen reads of trip 0 and end their half-block overlap)
+                    asm volatile("" : "+s"(sel.t_sh), "+s"(sel.thr_sh));
+                    trip(std::integral_constant<int, 0>{}, b);
+                    trip(std::integral_constant<int, 1>{}, b + NW);
+                    if (NPRE == 3) trip(std::integral_constant<int, 2>{}, b + 2 * NW);
+                }
             }
             if (t == 0) walk_state_finish(a, t_walk, i_end - i_begin, walk_mean);
             walk_mean = -1;

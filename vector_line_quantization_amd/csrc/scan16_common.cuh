@@ -51,6 +51,51 @@ __device__ __forceinline__ void load_query_table16(const ScanArgs& a, int64_t q,
     }
 }
 
+// The same for the float4 I0 .. I1 - 1 of the thread only: a caller that stores the table as it is produced asks for it in
+// parts (scan16_kernel's stored-sums set-up).  A copy, not the implementation of the function above: the kernels that call
+// that one compile to the code they had.
+template <int NI, int I0, int I1>
+__device__ __forceinline__ void load_query_table16_range(const ScanArgs& a, int64_t q, int t, int lane,
+                                                         int wave, float4 (&m2t3)[NI]) {
+    constexpr int E = 4096;
+    constexpr int NT = 1024 / NI;     // threads per workgroup
+    constexpr int NWV = NT / 64;      // waves per workgroup
+    if (a.qtab) {
+        const float4* qt = reinterpret_cast<const float4*>(a.qtab + q * E);
+#pragma unroll
+        for (int i = I0; i < I1; i++) {
+            const float4 v = qt[i * NT + t];
+            m2t3[i] = a.qtab_scaled ? v
+                                    : make_float4(__fmul_rn(-2.f, v.x), __fmul_rn(-2.f, v.y), __fmul_rn(-2.f, v.z),
+                                                  __fmul_rn(-2.f, v.w));
+        }
+    } else {
+        // codebook read from its transposed copy pq_cent_t[m][component][j]: the four
+        // centroids j = 4*lane..4*lane+3 of one component are one 16-byte load, a wave
+        // reads 1 KiB contiguous per instruction
+        const float* qv = a.queries + q * 128;
+#pragma unroll
+        for (int i = I0; i < I1; i++) {
+            const int m = NWV * i + wave;
+            const float4* ct = reinterpret_cast<const float4*>(a.pq_cent_t + (size_t)m * 8 * 256) + lane;
+            const float4 x0 = *reinterpret_cast<const float4*>(qv + m * 8);
+            const float4 x1 = *reinterpret_cast<const float4*>(qv + m * 8 + 4);
+            const float4 y0 = ct[0 * 64], y1 = ct[1 * 64], y2 = ct[2 * 64], y3 = ct[3 * 64];
+            const float4 y4 = ct[4 * 64], y5 = ct[5 * 64], y6 = ct[6 * 64], y7 = ct[7 * 64];
+            // fvec_inner_product, d = 8 (utils.cpp:509-533): s_l = ((0 + x_l y_l) + x_{l+4} y_{l+4}) + 0,
+            // result (s0+s1)+(s2+s3); .x/.y/.z/.w = centroids 4*lane+0..3
+#define VLQ_IP8(C)                                                                                        \
+    __fmul_rn(-2.f,                                                                                      \
+              __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(x0.x, y0.C)), __fmul_rn(x1.x, y4.C)), 0.f), \
+                                  __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(x0.y, y1.C)), __fmul_rn(x1.y, y5.C)), 0.f)), \
+                        __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(x0.z, y2.C)), __fmul_rn(x1.z, y6.C)), 0.f), \
+                                  __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(x0.w, y3.C)), __fmul_rn(x1.w, y7.C)), 0.f))))
+            m2t3[i] = make_float4(VLQ_IP8(x), VLQ_IP8(y), VLQ_IP8(z), VLQ_IP8(w));
+#undef VLQ_IP8
+        }
+    }
+}
+
 // dis = dis0 + tab[0][c0] + ... + tab[15][c15], strictly left to right
 // (IndexIVFPQ.cpp:788-794); L = LUT [16][256] in LDS, cc = one 16-byte code
 __device__ __forceinline__ float adc16(const float* L, const uint4 cc, float dis) {
