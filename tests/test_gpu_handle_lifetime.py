@@ -10,7 +10,7 @@ import vector_line_quantization_amd as vlq
 pytestmark = pytest.mark.gpu
 
 D_, M_, NBITS, NLIST, NB, NQ, NPROBE, K = 32, 8, 8, 16, 2000, 64, 4, 10
-KINDS = ("l2", "ip", "polysemous", "ivfpqr", "imi", "line")
+KINDS = ("l2", "ip", "polysemous", "ivfpqr", "imi", "line", "ivfflat", "ivfsq")
 
 
 def world():
@@ -32,13 +32,21 @@ def one_cycle(kind, w):
         g.set_coarse_centroids(w["coarse"])
         g.build_graph()
         g.set_lambda_codebook(w["lambda"])
+    elif kind == "ivfflat":
+        g = vlq.GpuIVFFlat(D_, NLIST)
+        g.set_coarse_centroids(w["coarse"])
+    elif kind == "ivfsq":
+        g = vlq.GpuIVFSQ(D_, NLIST, "8bit")
+        g.set_coarse_centroids(w["coarse"])
+        g.train(w["xb"])
     else:
         g = vlq.GpuIVFPQ(D_, NLIST, M_, NBITS, metric="ip" if kind == "ip" else "l2")
         if kind == "imi":
             g.set_imi_centroids(2, w["imi"])
         else:
             g.set_coarse_centroids(w["coarse"])
-    g.set_pq_centroids(w["pq"])
+    if kind not in ("ivfflat", "ivfsq"):
+        g.set_pq_centroids(w["pq"])
     if kind == "polysemous":
         g.set_polysemous_ht(28)
     if kind == "ivfpqr":

@@ -109,15 +109,6 @@ int read_bad_key(vlq_ivfpq_t h) {
     return bad_flag_error(bad);
 }
 
-vlq::ListStore list_store(vlq_ivfpq_t h) {
-    vlq::ListStore ls;
-    ls.nlist = h->nlist; ls.code_size = h->M;
-    ls.codes = &h->codes; ls.ids = &h->ids; ls.off = &h->list_off; ls.len = &h->list_len;
-    ls.h_off = &h->h_list_off; ls.h_len = &h->h_list_len; ls.h_stale = &h->h_lists_stale;
-    if (h->have_rpq) { ls.lambdas = &h->rcodes; ls.side_size = h->Mr; }    // IVFPQR: the refine codes move with the PQ codes
-    return ls;
-}
-
 }  // namespace vlq_detail
 
 extern "C" {
@@ -156,18 +147,12 @@ int vlq_ivfpq_create(vlq_ivfpq_t* out, int device, int d, int nlist, int M, int 
         if (m >= 0 && m <= 4) h->scan_schedule = m;
     }
     if (const char* e = getenv("VLQ_COARSE_FILTER")) h->coarse_filter = atoi(e);   // 1: filtered coarse stage (A/B; slower)
-    h->h_lists_stale = true;    // host copies of the list starts / lengths are filled on first use
     int rc = h->stats.reserve(512);    // [0] ncode, [1] flag word; [2..7] phase clocks of instrumented builds (-DVLQ_PHASE_TIMING), [8..47] (-DVLQ_SCAN16_PHASES)
     if (rc == VLQ_OK) rc = h->poly_stats.reserve(8);
-    if (rc == VLQ_OK) rc = h->list_off.reserve(((size_t)nlist + 1) * 8);
-    if (rc == VLQ_OK) rc = h->list_len.reserve((size_t)nlist * 8);
-    if (rc == VLQ_OK) rc = h->codes.reserve(16);
-    if (rc == VLQ_OK) rc = h->ids.reserve(16);
+    if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, nlist, M, 0, h->stream);
     if (rc != VLQ_OK) { vlq_ivfpq_destroy(h); return rc; }
     (void)hipMemsetAsync(h->stats.p, 0, 512, h->stream);
     (void)hipMemsetAsync(h->poly_stats.p, 0, 8, h->stream);
-    (void)hipMemsetAsync(h->list_off.p, 0, ((size_t)nlist + 1) * 8, h->stream);
-    (void)hipMemsetAsync(h->list_len.p, 0, (size_t)nlist * 8, h->stream);
     (void)hipStreamSynchronize(h->stream);
     h->have_lists = true;   // an empty index is searchable (all lists empty)
     *out = h;
@@ -424,35 +409,10 @@ int vlq_ivfpq_set_lists(vlq_ivfpq_t h, const uint8_t* codes, const int64_t* ids,
                         const int64_t* list_offsets) {
     if (!h || !list_offsets) return fail(VLQ_ERR_INVALID, "null argument");
     TRY(set_dev(h));
-    std::vector<int64_t> off((size_t)h->nlist + 1);
-    HIP_TRY(hipMemcpy(off.data(), list_offsets, off.size() * 8, hipMemcpyDefault));
-    if (off[0] != 0) return fail(VLQ_ERR_INVALID, "list_offsets[0] != 0");
-    for (int i = 0; i < h->nlist; i++) {
-        if (off[i + 1] < off[i]) return fail(VLQ_ERR_INVALID, "list_offsets not monotone at %d", i);
-        if (off[i + 1] - off[i] >= (int64_t(1) << 31))
-            return fail(VLQ_ERR_UNSUPPORTED, "list %d longer than 2^31", i);
-    }
-    const int64_t ntotal = off[h->nlist];
-    if (ntotal > 0 && (!codes || !ids)) return fail(VLQ_ERR_INVALID, "null codes/ids");
-    TRY(h->codes.reserve((size_t)ntotal * h->M + 16));
-    TRY(h->ids.reserve((size_t)ntotal * 8 + 16));
-    if (h->have_rpq) {          // new lists come without refine codes (vlq_ivfpq_set_refine_codes follows)
-        TRY(h->rcodes.reserve((size_t)ntotal * h->Mr + 16));
-        h->have_rcodes = ntotal == 0;
-    }
-    if (ntotal > 0) {
-        HIP_TRY(hipMemcpyAsync(h->codes.p, codes, (size_t)ntotal * h->M, hipMemcpyDefault, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->ids.p, ids, (size_t)ntotal * 8, hipMemcpyDefault, h->stream));
-    }
-    std::vector<int64_t> len((size_t)h->nlist);
-    for (int i = 0; i < h->nlist; i++) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];   // packed: capacity == length
-    HIP_TRY(hipMemcpyAsync(h->list_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->list_len.p, len.data(), len.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->h_list_off = off;
-    h->h_list_len.swap(len);
-    h->h_lists_stale = false;
+    int64_t ntotal = 0;
+    TRY(vlq::lists_load(h->lists, codes, nullptr, ids, list_offsets, "list_offsets", vlq::kIvfLenLimit, h->stream, &ntotal));
     h->ntotal = ntotal;
+    if (h->have_rpq) h->have_rcodes = h->ntotal == 0;    // new lists come without refine codes (vlq_ivfpq_set_refine_codes follows)
     h->have_lists = true;
     sums_invalidate(h);
     return finish_index_build(h);
@@ -463,30 +423,15 @@ int64_t vlq_ivfpq_ntotal(vlq_ivfpq_t h) { return h ? h->ntotal : -1; }
 int vlq_ivfpq_list_length(vlq_ivfpq_t h, int list_id, int64_t* len) {
     if (!h || !len) return fail(VLQ_ERR_INVALID, "null argument");
     if (list_id < 0 || list_id >= h->nlist) return fail(VLQ_ERR_INVALID, "list id out of range");
-    if (h->h_lists_stale) {
-        TRY(set_dev(h));
-        vlq::ListStore ls = list_store(h);
-        TRY(vlq::lists_sync_host(ls, h->stream));
-    }
-    *len = h->h_list_len[list_id];
-    return VLQ_OK;
+    TRY(set_dev(h));
+    return vlq::lists_length(h->lists, list_id, len, h->stream);
 }
 
 int vlq_ivfpq_get_list(vlq_ivfpq_t h, int list_id, uint8_t* codes_out, int64_t* ids_out) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (list_id < 0 || list_id >= h->nlist) return fail(VLQ_ERR_INVALID, "list id out of range");
     TRY(set_dev(h));
-    {
-        vlq::ListStore ls = list_store(h);
-        TRY(vlq::lists_sync_host(ls, h->stream));
-    }
-    const int64_t o = h->h_list_off[list_id], len = h->h_list_len[list_id];
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (len > 0 && codes_out)
-        HIP_TRY(hipMemcpy(codes_out, h->codes.as<uint8_t>() + o * h->M, (size_t)len * h->M, hipMemcpyDeviceToHost));
-    if (len > 0 && ids_out)
-        HIP_TRY(hipMemcpy(ids_out, h->ids.as<int64_t>() + o, (size_t)len * 8, hipMemcpyDeviceToHost));
-    return VLQ_OK;
+    return vlq::lists_read(h->lists, list_id, codes_out, nullptr, ids_out, h->stream);
 }
 
 int vlq_ivfpq_coarse_search(vlq_ivfpq_t h, int64_t n, const float* x, int nprobe,
@@ -805,8 +750,7 @@ int vlq_ivfpq_add(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* xids)
     }
     const void* idd = nullptr;
     if (xids) TRY(stage_in(h, xids, (size_t)n * 8, h->ws_keys_in, &idd));
-    vlq::ListStore ls = list_store(h);
-    TRY(vlq::lists_append(ls, h->ws_append, n, h->ws_assign.as<int64_t>(), nullptr, h->ws_codes.as<uint8_t>(),
+    TRY(vlq::lists_append(h->lists, n, h->ws_assign.as<int64_t>(), nullptr, h->ws_codes.as<uint8_t>(),
                           h->have_rpq ? h->ws_rcodes.as<uint8_t>() : nullptr, (const int64_t*)idd, h->ntotal, h->stream));
     if (h->have_rpq) h->have_rcodes = true;
     h->ntotal += n;                                             // IndexIVFPQ.cpp:271
@@ -819,17 +763,15 @@ int vlq_ivfpq_add(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* xids)
 int vlq_ivfpq_reserve_memory(vlq_ivfpq_t h, int64_t num_vecs) {
     if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument");
     TRY(set_dev(h));
-    vlq::ListStore ls = list_store(h);
     sums_invalidate(h);
-    return vlq::lists_reserve(ls, num_vecs, h->stream);
+    return vlq::lists_reserve(h->lists, num_vecs, h->stream);
 }
 
 int vlq_ivfpq_reclaim_memory(vlq_ivfpq_t h, uint64_t* bytes_reclaimed) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     TRY(set_dev(h));
-    vlq::ListStore ls = list_store(h);
     sums_invalidate(h);
-    return vlq::lists_reclaim(ls, bytes_reclaimed, h->stream);
+    return vlq::lists_reclaim(h->lists, bytes_reclaimed, h->stream);
 }
 
 }  // extern "C"

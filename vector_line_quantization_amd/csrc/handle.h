@@ -74,9 +74,24 @@ inline bool is_device_ptr(const void* p) {
 }  // namespace vlq_detail
 using namespace vlq_detail;
 
-struct AppendWs {   // lists.h AppendWorkspace (kept opaque here: handle.h is included by lists.h)
-    DevBuf cnt, cstart, keys_in, keys_out, sort_tmp;
+// Device-resident inverted lists (lists.h has the layout and the functions): the owner of their buffers, embedded by value
+// as `lists` in every index handle.  Not copyable (DevBuf is not).
+namespace vlq {
+struct ListStore {
+    int64_t nlist = 0;
+    int code_size = 0;
+    int side_size = 0;              // bytes per vector of the second field; 0 = none (VLQ: the lambda byte, 1; IVFPQR: the refine
+                                    // code of M_refine bytes, IndexIVFPQ.h:200-202, stored by list slot beside `codes`)
+    DevBuf codes;                   // [cap_total][code_size]
+    DevBuf side;                    // [cap_total][side_size]
+    DevBuf ids;                     // [cap_total] int64
+    DevBuf off;                     // [nlist+1] int64 list starts (off[nlist] = cap_total)
+    DevBuf len;                     // [nlist] int64
+    std::vector<int64_t> h_off, h_len;   // host copies of off / len for the per-list accessors, refreshed on demand
+    bool h_stale = true;                 // (lists_sync_host): stale until the first load, and after a device-side append
+    struct { DevBuf cnt, cstart, keys_in, keys_out, sort_tmp; } ws;   // lists_append's workspace
 };
+}  // namespace vlq
 
 struct vlq_ivfpq_s {
     int device = 0, d = 0, nlist = 0, M = 0, nbits = 0, ksub = 0, dsub = 0;
@@ -87,8 +102,8 @@ struct vlq_ivfpq_s {
     int64_t ntotal = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
 
-    // inverted lists: list i at [list_off[i], list_off[i] + list_len[i]), capacity list_off[i+1] - list_off[i]
-    DevBuf coarse, cnorm, pq, pq_t, rnorm, term2, codes, ids, list_off, list_len;
+    vlq::ListStore lists;         // the inverted lists; IVFPQR: lists.side holds the refine codes (side_size = Mr)
+    DevBuf coarse, cnorm, pq, pq_t, rnorm, term2;
     DevBuf list_rank;             // [nlist] int: spatial order of the lists (query scheduling only)
     DevBuf list_part;             // [nlist] u8: partition 0..7 of neighbouring lists, one per XCD (list-owned schedule)
     bool have_rank = false;
@@ -126,13 +141,10 @@ struct vlq_ivfpq_s {
     int imi_nbits = 0;
     DevBuf imi_cent, imi_norm, imi_virtual, ws_imi;
     bool have_coarse = false, have_pq = false, term2_valid = false, have_lists = false;
-    std::vector<int64_t> h_list_off, h_list_len;   // host copies, refreshed on demand (lists_sync_host)
-    bool h_lists_stale = false;
-    AppendWs ws_append;
-    // IVFPQR (IndexIVFPQ.h:200-225): the refine quantizer and its codes, stored by list slot beside `codes` (same starts,
-    // lengths and capacities: refine code of slot s at rcodes[s * Mr]).  have_rcodes: every stored vector has one.
+    // IVFPQR (IndexIVFPQ.h:200-225): the refine quantizer; its codes are the lists' side field (same starts, lengths and
+    // capacities: refine code of slot s at lists.side[s * Mr]).  have_rcodes: every stored vector has one.
     int Mr = 0, nbits_r = 0, ksub_r = 0, dsub_r = 0;
-    DevBuf rpq, rcodes;
+    DevBuf rpq;
     bool have_rpq = false, have_rcodes = false;
     DevBuf ws_sl, ws_Dsl, ws_r2, ws_rcodes;   // shortlist labels / distances of search_refined, r2 and refine codes of an add batch
 
@@ -157,7 +169,7 @@ struct vlq_ivfpq_s {
     bool fp16_tables = false, term2h_valid = false;
     DevBuf term2h, ws_qtabh;
     DevBuf stats;   // [0] ncode (u64), [1] bad key flag (int)
-    // Stored table sums of the 16-byte scan (scan16.hip, scan_sum_bound.h): one float per code slot of `codes` (the code's 16
+    // Stored table sums of the 16-byte scan (scan16.hip, scan_sum_bound.h): one float per code slot of `lists.codes` (the code's 16
     // term-2 entries added up) and one per list (t2abs).  They depend on the codebooks, the centroids and the list layout:
     // whatever changes one of those calls sums_invalidate(), ensure_code_sums() (scan_stage.hip) rebuilds them -- with the
     // lists' arrival, and lazily before a scan.  scan_sums: 0 = stored rows, 1 = automatic (vlq_ivfpq_set_scan_sums).
@@ -187,7 +199,6 @@ struct vlq_ivfpq_s {
 
 
 // internal entry points: what crosses the host files
-namespace vlq { struct ListStore; }   // lists.h
 namespace vlq_detail {
 // api.hip: staging and the checks the entry points share
 int set_dev(vlq_ivfpq_t h);
@@ -206,7 +217,6 @@ struct StagedRows {
 int check_ready(vlq_ivfpq_t h, bool need_lists);
 int check_search_args(vlq_ivfpq_t h, int64_t n, const void* x, int nprobe, int k, const void* D, const void* I);
 int read_bad_key(vlq_ivfpq_t h);
-vlq::ListStore list_store(vlq_ivfpq_t h);
 // scan_stage.hip
 struct StageTimer {      // books the stream time between its construction and stop() to a stage (vlq_ivfpq_profile)
     vlq_ivfpq_t h; int stage; hipEvent_t a = nullptr, b = nullptr;

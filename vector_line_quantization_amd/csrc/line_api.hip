@@ -10,7 +10,8 @@ struct vlq_line_s {
     vlq_ivfpq_t base = nullptr;          // coarse centroids, PQ, term2, workspace, stream
     int nedge = 0, nlambda = 0;
     int64_t nlines = 0, ntotal = 0, ntotal_added = 0;
-    DevBuf edge_info, edge_dist, lambda_info, codes, lambdas, ids, line_off, line_len;   // lists.h layout
+    DevBuf edge_info, edge_dist, lambda_info;
+    vlq::ListStore lists;                // one list per line; the side field is the lambda byte
     bool have_graph = false, have_lambda = false;
     // float16 look-up tables (GpuIndexIVFPQConfig::useFloat16LookupTables): half(term2), built on demand
     bool fp16_tables = false, term2h_valid = false;
@@ -27,9 +28,6 @@ struct vlq_line_s {
     // they depend on changed (codes / lambda bytes / line layout, term 2 = coarse + PQ centroids, graph, lambda codebook)
     DevBuf pconst, pconsth, ws_part_keys;
     bool pconst_valid = false, pconsth_valid = false;
-    std::vector<int64_t> h_line_off, h_line_len;
-    bool h_lines_stale = false;
-    AppendWs ws_append;
     std::vector<float> h_lambda;
     DevBuf ws_near, ws_line, ws_lamf, ws_lamb, ws_res, ws_codes, ws_sel_line, ws_sel_b2, ws_sel_g, ws_sel_meta, ws_sel_cnt,
         ws_x, ws_D, ws_I, ws_keys, ws_cdis, stats;
@@ -99,15 +97,15 @@ int ensure_consts(vlq_line_t h, bool fp16, bool* have, const int* newcnt = nullp
     DevBuf& buf = fp16 ? h->pconsth : h->pconst;
     DevBuf& other = fp16 ? h->pconst : h->pconsth;
     if (other.p) { other.release(); (fp16 ? h->pconst_valid : h->pconsth_valid) = false; }
-    if (newcnt && buf.cap < h->codes.cap / (size_t)b->M * 4 + 16) newcnt = nullptr;      // (a grown buffer starts empty: everything)
-    if (buf.reserve(h->codes.cap / (size_t)b->M * 4 + 16) != VLQ_OK) {      // one float per code slot of the current layout
+    if (newcnt && buf.cap < h->lists.codes.cap / (size_t)b->M * 4 + 16) newcnt = nullptr;      // (a grown buffer starts empty: everything)
+    if (buf.reserve(h->lists.codes.cap / (size_t)b->M * 4 + 16) != VLQ_OK) {      // one float per code slot of the current layout
         (void)hipGetLastError();
         valid = false;
         *have = false;
         return VLQ_OK;
     }
-    vlq::launch_line_consts(h->codes.as<uint8_t>(), h->lambdas.as<uint8_t>(), h->line_off.as<int64_t>(),
-                            h->line_len.as<int64_t>(), h->edge_info.as<int32_t>(), b->term2.as<float>(),
+    vlq::launch_line_consts(h->lists.codes.as<uint8_t>(), h->lists.side.as<uint8_t>(), h->lists.off.as<int64_t>(),
+                            h->lists.len.as<int64_t>(), h->edge_info.as<int32_t>(), b->term2.as<float>(),
                             fp16 ? h->term2h.as<uint16_t>() : nullptr, h->lambda_info.as<float>(), h->nedge, b->M, b->ksub,
                             h->nlines, buf.as<float>(), b->stream, newcnt);
     HIP_TRY(hipGetLastError());
@@ -118,14 +116,6 @@ int ensure_consts(vlq_line_t h, bool fp16, bool* have, const int* newcnt = nullp
 void drop_consts(vlq_line_t h) { h->pconst_valid = h->pconsth_valid = false; }
 
 }  // namespace
-
-static vlq::ListStore line_store(vlq_line_t h) {
-    vlq::ListStore ls;
-    ls.nlist = h->nlines; ls.code_size = h->base->M;
-    ls.codes = &h->codes; ls.lambdas = &h->lambdas; ls.ids = &h->ids; ls.off = &h->line_off; ls.len = &h->line_len;
-    ls.h_off = &h->h_line_off; ls.h_len = &h->h_line_len; ls.h_stale = &h->h_lines_stale;
-    return ls;
-}
 
 extern "C" {
 
@@ -142,16 +132,9 @@ int vlq_line_create(vlq_line_t* out, int device, int d, int nlist, int M, int nb
     int rc = vlq_ivfpq_create(&h->base, device, d, nlist, M, nbits);
     if (rc != VLQ_OK) { delete h; return rc; }
     h->nedge = nedge; h->nlambda = nlambda; h->nlines = (int64_t)nlist * nedge;
-    h->h_lines_stale = true;    // host copies are filled on first use
-    rc = h->line_off.reserve(((size_t)h->nlines + 1) * 8);
-    if (rc == VLQ_OK) rc = h->line_len.reserve((size_t)h->nlines * 8);
-    if (rc == VLQ_OK) rc = h->stats.reserve(64);
-    if (rc == VLQ_OK) rc = h->codes.reserve(16);
-    if (rc == VLQ_OK) rc = h->lambdas.reserve(16);
-    if (rc == VLQ_OK) rc = h->ids.reserve(16);
+    rc = h->stats.reserve(64);
+    if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, h->nlines, M, 1, h->base->stream);
     if (rc != VLQ_OK) { vlq_line_destroy(h); return rc; }
-    (void)hipMemsetAsync(h->line_off.p, 0, ((size_t)h->nlines + 1) * 8, h->base->stream);
-    (void)hipMemsetAsync(h->line_len.p, 0, (size_t)h->nlines * 8, h->base->stream);
     (void)hipMemsetAsync(h->stats.p, 0, 64, h->base->stream);
     (void)hipStreamSynchronize(h->base->stream);
     *out = h;
@@ -334,29 +317,11 @@ int vlq_line_set_lists(vlq_line_t h, const uint8_t* codes, const uint8_t* lambda
     vlq_ivfpq_t b = h->base;
     TRY(set_dev(b));
     drop_consts(h);
-    std::vector<int64_t> off((size_t)h->nlines + 1);
-    HIP_TRY(hipMemcpy(off.data(), line_offsets, off.size() * 8, hipMemcpyDefault));
-    if (off[0] != 0) return fail(VLQ_ERR_INVALID, "line_offsets[0] != 0");
-    for (int64_t i = 0; i < h->nlines; i++)
-        if (off[i + 1] < off[i]) return fail(VLQ_ERR_INVALID, "line_offsets not monotone at %ld", (long)i);
-    const int64_t nt = off[h->nlines];
-    if (nt > 0 && (!codes || !lambdas || !ids)) return fail(VLQ_ERR_INVALID, "null codes/lambdas/ids");
-    TRY(h->codes.reserve((size_t)nt * b->M + 16));
-    TRY(h->lambdas.reserve((size_t)nt + 16));
-    TRY(h->ids.reserve((size_t)nt * 8 + 16));
-    if (nt > 0) {
-        HIP_TRY(hipMemcpyAsync(h->codes.p, codes, (size_t)nt * b->M, hipMemcpyDefault, b->stream));
-        HIP_TRY(hipMemcpyAsync(h->lambdas.p, lambdas, (size_t)nt, hipMemcpyDefault, b->stream));
-        HIP_TRY(hipMemcpyAsync(h->ids.p, ids, (size_t)nt * 8, hipMemcpyDefault, b->stream));
-    }
-    std::vector<int64_t> len((size_t)h->nlines);
-    for (int64_t i = 0; i < h->nlines; i++) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
-    HIP_TRY(hipMemcpyAsync(h->line_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(h->line_len.p, len.data(), len.size() * 8, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    h->h_line_off.swap(off);
-    h->h_line_len.swap(len);
-    h->h_lines_stale = false;
+    int64_t nt = 0;
+    // (null lambdas are refused like null codes)
+    const int rc = vlq::lists_load(h->lists, lambdas ? codes : nullptr, lambdas, ids, line_offsets, "line_offsets", vlq::kNoLenLimit,
+                                   b->stream, &nt);
+    if (rc != VLQ_OK) return nt > 0 && (!codes || !lambdas || !ids) ? fail(VLQ_ERR_INVALID, "null codes/lambdas/ids") : rc;
     h->ntotal = nt;
     h->ntotal_added = nt;        // sequential ids continue from the loaded count (IndexIVFPQ.cpp:244)
     return VLQ_OK;
@@ -375,10 +340,9 @@ int vlq_line_add(vlq_line_t h, int64_t n, const float* x, const int64_t* xids) {
     TRY(encode_dev(h, n, (const float*)xd));
     const void* idd = nullptr;
     if (xids) TRY(stage_in(b, xids, (size_t)n * 8, h->ws_keys, &idd));
-    vlq::ListStore ls = line_store(h);
     int64_t placed = 0;
     bool relaid = false;
-    const int rc = vlq::lists_append(ls, h->ws_append, n, nullptr, h->ws_line.as<int32_t>(), h->ws_codes.as<uint8_t>(),
+    const int rc = vlq::lists_append(h->lists, n, nullptr, h->ws_line.as<int32_t>(), h->ws_codes.as<uint8_t>(),
                                      h->ws_lamb.as<uint8_t>(), (const int64_t*)idd, h->ntotal_added, b->stream, &placed, &relaid);
     if (rc != VLQ_OK) { drop_consts(h); return rc; }
     h->ntotal += placed;         // vectors without a line are dropped
@@ -390,7 +354,7 @@ int vlq_line_add(vlq_line_t h, int64_t n, const float* x, const int64_t* xids) {
         for (int fp16 = 0; fp16 < 2; fp16++) {
             if (!(fp16 ? h->pconsth_valid : h->pconst_valid)) continue;
             bool have = false;
-            TRY(ensure_consts(h, fp16 != 0, &have, h->ws_append.cnt.as<int>()));
+            TRY(ensure_consts(h, fp16 != 0, &have, h->lists.ws.cnt.as<int>()));
         }
     }
     return VLQ_OK;
@@ -401,30 +365,15 @@ int64_t vlq_line_ntotal(vlq_line_t h) { return h ? h->ntotal : -1; }
 int vlq_line_list_length(vlq_line_t h, int64_t line, int64_t* len) {
     if (!h || !len) return fail(VLQ_ERR_INVALID, "null argument");
     if (line < 0 || line >= h->nlines) return fail(VLQ_ERR_INVALID, "line id out of range");
-    if (h->h_lines_stale) {
-        TRY(set_dev(h->base));
-        vlq::ListStore ls = line_store(h);
-        TRY(vlq::lists_sync_host(ls, h->base->stream));
-    }
-    *len = h->h_line_len[line];
-    return VLQ_OK;
+    TRY(set_dev(h->base));
+    return vlq::lists_length(h->lists, line, len, h->base->stream);
 }
 
 int vlq_line_get_list(vlq_line_t h, int64_t line, uint8_t* codes_out, uint8_t* lambdas_out, int64_t* ids_out) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (line < 0 || line >= h->nlines) return fail(VLQ_ERR_INVALID, "line id out of range");
-    vlq_ivfpq_t b = h->base;
-    TRY(set_dev(b));
-    {
-        vlq::ListStore ls = line_store(h);
-        TRY(vlq::lists_sync_host(ls, b->stream));
-    }
-    const int64_t o = h->h_line_off[line], len = h->h_line_len[line];
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (len > 0 && codes_out) HIP_TRY(hipMemcpy(codes_out, h->codes.as<uint8_t>() + o * b->M, (size_t)len * b->M, hipMemcpyDeviceToHost));
-    if (len > 0 && lambdas_out) HIP_TRY(hipMemcpy(lambdas_out, h->lambdas.as<uint8_t>() + o, (size_t)len, hipMemcpyDeviceToHost));
-    if (len > 0 && ids_out) HIP_TRY(hipMemcpy(ids_out, h->ids.as<int64_t>() + o, (size_t)len * 8, hipMemcpyDeviceToHost));
-    return VLQ_OK;
+    TRY(set_dev(h->base));
+    return vlq::lists_read(h->lists, line, codes_out, lambdas_out, ids_out, h->base->stream);
 }
 
 int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1, int k, float* D,
@@ -485,13 +434,13 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
                 vlq::launch_line_select2(b->ws_dist.as<float>(), nj, b->nlist, h->ws_keys.as<int64_t>(), nprobe,
                                          h->edge_info.as<int32_t>(), h->edge_dist.as<float>(), h->nedge, w1,
                                          sel_line + j0 * w1, h->ws_sel_b2.as<float>() + j0 * w1, h->ws_sel_g.as<float>() + j0 * w1,
-                                         b->stream, h->line_off.as<int64_t>(), h->line_len.as<int64_t>(), VLQ_LINE_MAX_CODES,
+                                         b->stream, h->lists.off.as<int64_t>(), h->lists.len.as<int64_t>(), VLQ_LINE_MAX_CODES,
                                          metaj, h->ws_sel_cnt.as<int32_t>() + j0);
             else
                 vlq::launch_line_select(b->ws_dist.as<float>(), nj, b->nlist, h->ws_keys.as<int64_t>(), nprobe,
                                         h->edge_info.as<int32_t>(), h->edge_dist.as<float>(), h->nedge, w1,
                                         sel_line + j0 * w1, h->ws_sel_b2.as<float>() + j0 * w1, h->ws_sel_g.as<float>() + j0 * w1,
-                                        b->stream, h->line_off.as<int64_t>(), h->line_len.as<int64_t>(), VLQ_LINE_MAX_CODES,
+                                        b->stream, h->lists.off.as<int64_t>(), h->lists.len.as<int64_t>(), VLQ_LINE_MAX_CODES,
                                         metaj, h->ws_sel_cnt.as<int32_t>() + j0);
         }
         // the stored codes' share of the distance (line16c.hip), once per database state
@@ -507,8 +456,8 @@ int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1,
         }
         // 4. scan + top-k
         vlq::LineScanArgs a;
-        a.codes = h->codes.as<uint8_t>(); a.lambdas = h->lambdas.as<uint8_t>(); a.ids = h->ids.as<int64_t>();
-        a.line_off = h->line_off.as<int64_t>(); a.line_len = h->line_len.as<int64_t>(); a.term2 = rebuilt_rows ? nullptr : b->term2.as<float>(); a.qtab = b->ws_qtab.as<float>();
+        a.codes = h->lists.codes.as<uint8_t>(); a.lambdas = h->lists.side.as<uint8_t>(); a.ids = h->lists.ids.as<int64_t>();
+        a.line_off = h->lists.off.as<int64_t>(); a.line_len = h->lists.len.as<int64_t>(); a.term2 = rebuilt_rows ? nullptr : b->term2.as<float>(); a.qtab = b->ws_qtab.as<float>();
         a.edge_info = h->edge_info.as<int32_t>(); a.edge_dist = h->edge_dist.as<float>();
         a.lambda_info = h->lambda_info.as<float>();
         a.sel_line = sel_line; a.sel_b2 = h->ws_sel_b2.as<float>(); a.sel_g = h->ws_sel_g.as<float>();

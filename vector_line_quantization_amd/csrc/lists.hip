@@ -130,13 +130,79 @@ __global__ void place_kernel(const unsigned long long* __restrict__ sorted, int6
 
 // refresh the host copies of the list starts / lengths after device-side appends
 int lists_sync_host(ListStore& ls, hipStream_t s) {
-    if (!ls.h_stale || !*ls.h_stale) return VLQ_OK;
-    ls.h_off->resize((size_t)ls.nlist + 1);
-    ls.h_len->resize((size_t)ls.nlist);
-    HIP_TRY(hipMemcpyAsync(ls.h_off->data(), ls.off->p, ((size_t)ls.nlist + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ls.h_len->data(), ls.len->p, (size_t)ls.nlist * 8, hipMemcpyDeviceToHost, s));
+    if (!ls.h_stale) return VLQ_OK;
+    ls.h_off.resize((size_t)ls.nlist + 1);
+    ls.h_len.resize((size_t)ls.nlist);
+    HIP_TRY(hipMemcpyAsync(ls.h_off.data(), ls.off.p, ((size_t)ls.nlist + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ls.h_len.data(), ls.len.p, (size_t)ls.nlist * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    *ls.h_stale = false;
+    ls.h_stale = false;
+    return VLQ_OK;
+}
+
+int lists_init(ListStore& ls, int64_t nlist, int code_size, int side_size, hipStream_t s) {
+    ls.nlist = nlist; ls.code_size = code_size; ls.side_size = side_size;
+    TRY(ls.off.reserve(((size_t)nlist + 1) * 8));
+    TRY(ls.len.reserve((size_t)nlist * 8));
+    TRY(ls.codes.reserve(16));
+    if (side_size) TRY(ls.side.reserve(16));
+    TRY(ls.ids.reserve(16));
+    return lists_clear(ls, s);
+}
+
+int lists_clear(ListStore& ls, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(ls.off.p, 0, ((size_t)ls.nlist + 1) * 8, s));
+    HIP_TRY(hipMemsetAsync(ls.len.p, 0, (size_t)ls.nlist * 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ls.h_stale = true;
+    return VLQ_OK;
+}
+
+int lists_load(ListStore& ls, const void* codes, const void* side, const int64_t* ids, const int64_t* offsets, const char* noun,
+               int64_t len_limit, hipStream_t s, int64_t* ntotal) {
+    const size_t nlist = (size_t)ls.nlist;
+    std::vector<int64_t> off(nlist + 1), len(nlist);
+    HIP_TRY(hipMemcpy(off.data(), offsets, off.size() * 8, hipMemcpyDefault));
+    char msg[128];
+    const int bad = check_list_offsets(off.data(), ls.nlist, noun, len_limit, msg, sizeof(msg));
+    if (bad != VLQ_OK) return fail(bad, "%s", msg);
+    const int64_t nt = off[nlist];
+    *ntotal = nt;
+    if (nt > 0 && (!codes || !ids)) return fail(VLQ_ERR_INVALID, "null codes/ids");
+    HIP_TRY(hipStreamSynchronize(s));       // growth frees the old blocks
+    TRY(ls.codes.reserve((size_t)nt * ls.code_size + 16));
+    if (ls.side_size) TRY(ls.side.reserve((size_t)nt * ls.side_size + 16));
+    TRY(ls.ids.reserve((size_t)nt * 8 + 16));
+    if (nt > 0) {
+        HIP_TRY(hipMemcpyAsync(ls.codes.p, codes, (size_t)nt * ls.code_size, hipMemcpyDefault, s));
+        if (ls.side_size && side) HIP_TRY(hipMemcpyAsync(ls.side.p, side, (size_t)nt * ls.side_size, hipMemcpyDefault, s));
+        HIP_TRY(hipMemcpyAsync(ls.ids.p, ids, (size_t)nt * 8, hipMemcpyDefault, s));
+    }
+    for (size_t i = 0; i < nlist; i++) len[i] = off[i + 1] - off[i];   // packed: capacity == length
+    HIP_TRY(hipMemcpyAsync(ls.off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ls.len.p, len.data(), len.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ls.h_off.swap(off);
+    ls.h_len.swap(len);
+    ls.h_stale = false;
+    return VLQ_OK;
+}
+
+int lists_length(ListStore& ls, int64_t i, int64_t* len, hipStream_t s) {
+    TRY(lists_sync_host(ls, s));
+    *len = ls.h_len[(size_t)i];
+    return VLQ_OK;
+}
+
+int lists_read(ListStore& ls, int64_t i, void* codes_out, void* side_out, int64_t* ids_out, hipStream_t s) {
+    TRY(lists_sync_host(ls, s));
+    const size_t o = (size_t)ls.h_off[(size_t)i], len = (size_t)ls.h_len[(size_t)i];
+    HIP_TRY(hipStreamSynchronize(s));
+    if (len == 0) return VLQ_OK;
+    const size_t cs = (size_t)ls.code_size, ss = (size_t)ls.side_size;
+    if (codes_out) HIP_TRY(hipMemcpy(codes_out, ls.codes.as<uint8_t>() + o * cs, len * cs, hipMemcpyDeviceToHost));
+    if (side_out) HIP_TRY(hipMemcpy(side_out, ls.side.as<uint8_t>() + o * ss, len * ss, hipMemcpyDeviceToHost));
+    if (ids_out) HIP_TRY(hipMemcpy(ids_out, ls.ids.as<int64_t>() + o, len * 8, hipMemcpyDeviceToHost));
     return VLQ_OK;
 }
 
@@ -147,24 +213,24 @@ static int relayout_dev(ListStore& ls, DevBuf& noff, int64_t cap, hipStream_t s)
     DevBuf nc, nl, ni;
     int rc = nc.reserve((size_t)cap * ls.code_size + 16);
     if (rc == VLQ_OK) rc = ni.reserve((size_t)cap * 8 + 16);
-    if (rc == VLQ_OK && ls.lambdas) rc = nl.reserve((size_t)cap * ls.side_size + 16);
+    if (rc == VLQ_OK && ls.side_size) rc = nl.reserve((size_t)cap * ls.side_size + 16);
     if (rc != VLQ_OK) return rc;
     hipError_t e = hipSuccess;
-    if (ls.codes->p) {
+    if (ls.codes.p) {
         const unsigned g = (unsigned)((nlist + 255) / 256);
-        hipLaunchKernelGGL(relayout_kernel, dim3(g), dim3(256), 0, s, ls.codes->as<uint8_t>(),
-                           ls.lambdas ? ls.lambdas->as<uint8_t>() : nullptr, ls.ids->as<int64_t>(),
-                           ls.off->as<int64_t>(), ls.len->as<int64_t>(), noff.as<int64_t>(), nlist,
-                           ls.code_size, ls.side_size, nc.as<uint8_t>(), ls.lambdas ? nl.as<uint8_t>() : nullptr,
+        hipLaunchKernelGGL(relayout_kernel, dim3(g), dim3(256), 0, s, ls.codes.as<uint8_t>(),
+                           ls.side_size ? ls.side.as<uint8_t>() : nullptr, ls.ids.as<int64_t>(),
+                           ls.off.as<int64_t>(), ls.len.as<int64_t>(), noff.as<int64_t>(), nlist,
+                           ls.code_size, ls.side_size, nc.as<uint8_t>(), ls.side_size ? nl.as<uint8_t>() : nullptr,
                            ni.as<int64_t>());
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // the old buffers die below
     if (e != hipSuccess) return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e));
-    std::swap(*ls.codes, nc);
-    std::swap(*ls.ids, ni);
-    if (ls.lambdas) std::swap(*ls.lambdas, nl);
-    std::swap(*ls.off, noff);
+    std::swap(ls.codes, nc);
+    std::swap(ls.ids, ni);
+    if (ls.side_size) std::swap(ls.side, nl);
+    std::swap(ls.off, noff);
     return VLQ_OK;      // (the old blocks go with nc / nl / ni here, the old starts with the caller's noff)
 }
 
@@ -177,7 +243,7 @@ int lists_relayout(ListStore& ls, std::vector<int64_t>& new_off, hipStream_t s) 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(VLQ_ERR_HIP, "list relayout failed: %s", hipGetErrorString(e));
     TRY(relayout_dev(ls, noff, new_off[(size_t)nlist], s));
-    ls.h_off->swap(new_off);
+    ls.h_off.swap(new_off);
     return VLQ_OK;
 }
 
@@ -186,7 +252,7 @@ int lists_reserve(ListStore& ls, int64_t num_vecs, hipStream_t s) {
     const int64_t per = num_vecs / ls.nlist;
     if (per < 1) return VLQ_OK;
     TRY(lists_sync_host(ls, s));
-    const std::vector<int64_t>& h_off = *ls.h_off;
+    const std::vector<int64_t>& h_off = ls.h_off;
     bool change = false;
     std::vector<int64_t> new_off((size_t)ls.nlist + 1, 0);
     for (int64_t i = 0; i < ls.nlist; i++) {
@@ -201,19 +267,19 @@ int lists_reserve(ListStore& ls, int64_t num_vecs, hipStream_t s) {
 // *bytes = device bytes given back
 int lists_reclaim(ListStore& ls, uint64_t* bytes, hipStream_t s) {
     TRY(lists_sync_host(ls, s));
-    const std::vector<int64_t>& h_len = *ls.h_len;
-    const int64_t old_cap = (*ls.h_off)[(size_t)ls.nlist];
+    const std::vector<int64_t>& h_len = ls.h_len;
+    const int64_t old_cap = ls.h_off[(size_t)ls.nlist];
     std::vector<int64_t> new_off((size_t)ls.nlist + 1, 0);
     for (int64_t i = 0; i < ls.nlist; i++) new_off[(size_t)i + 1] = new_off[(size_t)i] + h_len[(size_t)i];
     const int64_t new_cap = new_off[(size_t)ls.nlist];
-    if (bytes) *bytes = (uint64_t)(old_cap - new_cap) * (uint64_t)(ls.code_size + 8 + (ls.lambdas ? ls.side_size : 0));
+    if (bytes) *bytes = (uint64_t)(old_cap - new_cap) * (uint64_t)(ls.code_size + 8 + ls.side_size);
     if (new_cap == old_cap) return VLQ_OK;
     return lists_relayout(ls, new_off, s);
 }
 
-int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* assign64,
-                 const int32_t* assign32, const uint8_t* new_codes, const uint8_t* new_lambdas,
-                 const int64_t* xids, int64_t id_base, hipStream_t s, int64_t* placed, bool* relaid) {
+int lists_append(ListStore& ls, int64_t n, const int64_t* assign64, const int32_t* assign32, const uint8_t* new_codes,
+                 const uint8_t* new_side, const int64_t* xids, int64_t id_base, hipStream_t s, int64_t* placed, bool* relaid) {
+    auto& ws = ls.ws;
     if (placed) *placed = 0;
     if (relaid) *relaid = false;
     if (n <= 0) return VLQ_OK;
@@ -252,8 +318,8 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
 
     // 2. room?  If any list overflows its capacity the layout is rebuilt with 25 % slack -- the
     //    per-list arithmetic stays on the device; the host sees one flag and two totals.
-    hipLaunchKernelGGL(overflow_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), ls.len->as<int64_t>(),
-                       ls.off->as<int64_t>(), nlist, flag);
+    hipLaunchKernelGGL(overflow_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), ls.len.as<int64_t>(),
+                       ls.off.as<int64_t>(), nlist, flag);
     HIP_TRY(hipGetLastError());
     int grow = 0;
     int64_t total = 0;
@@ -265,8 +331,8 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
         int rc = caps.reserve(((size_t)nlist + 1) * 8);
         if (rc == VLQ_OK) rc = noff.reserve(((size_t)nlist + 1) * 8);
         if (rc != VLQ_OK) return rc;
-        hipLaunchKernelGGL(grow_caps_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), ls.len->as<int64_t>(),
-                           ls.off->as<int64_t>(), nlist, caps.as<int64_t>());
+        hipLaunchKernelGGL(grow_caps_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), ls.len.as<int64_t>(),
+                           ls.off.as<int64_t>(), nlist, caps.as<int64_t>());
         size_t b2 = 0;
         hipError_t e = rocprim::exclusive_scan(nullptr, b2, caps.as<int64_t>(), noff.as<int64_t>(), (int64_t)0,
                                                (size_t)nlist + 1, rocprim::plus<int64_t>(), s);
@@ -285,12 +351,12 @@ int lists_append(ListStore& ls, AppendWorkspace& ws, int64_t n, const int64_t* a
 
     // 3. place the batch, then publish the new lengths
     hipLaunchKernelGGL(place_kernel, dim3(grid), dim3(256), 0, s, ws.keys_out.as<unsigned long long>(), n,
-                       ws.cstart.as<int64_t>(), ls.off->as<int64_t>(), ls.len->as<int64_t>(), new_codes,
-                       new_lambdas, xids, id_base, ls.code_size, ls.side_size, ls.codes->as<uint8_t>(),
-                       ls.lambdas ? ls.lambdas->as<uint8_t>() : nullptr, ls.ids->as<int64_t>());
-    hipLaunchKernelGGL(add_counts_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), nlist, ls.len->as<int64_t>());
+                       ws.cstart.as<int64_t>(), ls.off.as<int64_t>(), ls.len.as<int64_t>(), new_codes,
+                       new_side, xids, id_base, ls.code_size, ls.side_size, ls.codes.as<uint8_t>(),
+                       ls.side_size ? ls.side.as<uint8_t>() : nullptr, ls.ids.as<int64_t>());
+    hipLaunchKernelGGL(add_counts_kernel, dim3(lgrid), dim3(256), 0, s, ws.cnt.as<int>(), nlist, ls.len.as<int64_t>());
     HIP_TRY(hipGetLastError());
-    if (ls.h_stale) *ls.h_stale = true;
+    ls.h_stale = true;
     if (placed) *placed = total;
     return VLQ_OK;
 }

@@ -43,8 +43,8 @@ static int refine_k_coarse(int k, float k_factor, int* kc) {
 static int refine_dev(vlq_ivfpq_t h, int64_t n, const float* xd, const int64_t* sld, int k_coarse, int k, float* Dd, int64_t* Id) {
     vlq::RefineArgs a;
     a.x = xd; a.shortlist = sld; a.coarse = h->coarse.as<float>(); a.pq = h->pq.as<float>(); a.rpq = h->rpq.as<float>();
-    a.codes = h->codes.as<uint8_t>(); a.rcodes = h->rcodes.as<uint8_t>(); a.ids = h->ids.as<int64_t>();
-    a.list_off = h->list_off.as<int64_t>(); a.list_len = h->list_len.as<int64_t>();
+    a.codes = h->lists.codes.as<uint8_t>(); a.rcodes = h->lists.side.as<uint8_t>(); a.ids = h->lists.ids.as<int64_t>();
+    a.list_off = h->lists.off.as<int64_t>(); a.list_len = h->lists.len.as<int64_t>();
     a.D = Dd; a.I = Id; a.bad = reinterpret_cast<int*>(h->stats.as<char>() + 8);
     a.nq = n; a.k_coarse = k_coarse; a.k = k; a.d = h->d; a.nlist = h->nlist;
     a.M = h->M; a.ksub = h->ksub; a.dsub = h->dsub; a.Mr = h->Mr; a.ksub_r = h->ksub_r; a.dsub_r = h->dsub_r;
@@ -59,16 +59,16 @@ int vlq_ivfpq_set_refine_pq(vlq_ivfpq_t h, int M_refine, int nbits_refine, const
     if (M_refine < 1 || h->d % M_refine != 0) return fail(VLQ_ERR_INVALID, "d=%d not a multiple of M_refine=%d", h->d, M_refine);
     if (nbits_refine < 1 || nbits_refine > 8) return fail(VLQ_ERR_INVALID, "nbits_refine=%d outside 1..8", nbits_refine);
     TRY(set_dev(h));
-    vlq::ListStore ls = list_store(h);
-    TRY(vlq::lists_sync_host(ls, h->stream));
+    TRY(vlq::lists_sync_host(h->lists, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));      // (the old refine array may still be read)
     const size_t bytes = (size_t)h->d * (size_t)(1 << nbits_refine) * sizeof(float);
     TRY(h->rpq.reserve(bytes));
     HIP_TRY(hipMemcpyAsync(h->rpq.p, centroids, bytes, hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->Mr = M_refine; h->nbits_r = nbits_refine; h->ksub_r = 1 << nbits_refine; h->dsub_r = h->d / M_refine;
-    // one refine code per list slot, slack included
-    TRY(h->rcodes.reserve((size_t)h->h_list_off[(size_t)h->nlist] * h->Mr + 16));
+    // one refine code per list slot, slack included; from here on the lists carry them as their side field
+    TRY(h->lists.side.reserve((size_t)h->lists.h_off[(size_t)h->nlist] * h->Mr + 16));
+    h->lists.side_size = h->Mr;
     h->have_rpq = true;
     h->have_rcodes = h->ntotal == 0;
     return VLQ_OK;
@@ -78,20 +78,19 @@ int vlq_ivfpq_set_refine_codes(vlq_ivfpq_t h, const uint8_t* refine_codes) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (!h->have_rpq) return fail(VLQ_ERR_STATE, "refine quantizer not set (vlq_ivfpq_set_refine_pq)");
     TRY(set_dev(h));
-    vlq::ListStore ls = list_store(h);
-    TRY(vlq::lists_sync_host(ls, h->stream));
+    TRY(vlq::lists_sync_host(h->lists, h->stream));
     int64_t stored = 0;
-    for (int i = 0; i < h->nlist; i++) stored += h->h_list_len[(size_t)i];
+    for (int i = 0; i < h->nlist; i++) stored += h->lists.h_len[(size_t)i];
     if (stored > 0 && !refine_codes) return fail(VLQ_ERR_INVALID, "null refine codes");
     const size_t Mr = (size_t)h->Mr;
-    if (stored == h->h_list_off[(size_t)h->nlist]) {          // packed lists: one copy
-        if (stored > 0) HIP_TRY(hipMemcpyAsync(h->rcodes.p, refine_codes, (size_t)stored * Mr, hipMemcpyDefault, h->stream));
+    if (stored == h->lists.h_off[(size_t)h->nlist]) {          // packed lists: one copy
+        if (stored > 0) HIP_TRY(hipMemcpyAsync(h->lists.side.p, refine_codes, (size_t)stored * Mr, hipMemcpyDefault, h->stream));
     } else {                                                    // lists with append slack: list by list
         int64_t src = 0;
         for (int i = 0; i < h->nlist; i++) {
-            const int64_t len = h->h_list_len[(size_t)i];
+            const int64_t len = h->lists.h_len[(size_t)i];
             if (len > 0)
-                HIP_TRY(hipMemcpyAsync(h->rcodes.as<uint8_t>() + (size_t)h->h_list_off[(size_t)i] * Mr, refine_codes + (size_t)src * Mr,
+                HIP_TRY(hipMemcpyAsync(h->lists.side.as<uint8_t>() + (size_t)h->lists.h_off[(size_t)i] * Mr, refine_codes + (size_t)src * Mr,
                                        (size_t)len * Mr, hipMemcpyDefault, h->stream));
             src += len;
         }
@@ -107,13 +106,7 @@ int vlq_ivfpq_get_list_refine_codes(vlq_ivfpq_t h, int list_id, uint8_t* out) {
     if (!h->have_rpq) return fail(VLQ_ERR_STATE, "refine quantizer not set (vlq_ivfpq_set_refine_pq)");
     if (h->ntotal > 0 && !h->have_rcodes) return fail(VLQ_ERR_STATE, "the stored vectors have no refine codes (vlq_ivfpq_set_refine_codes)");
     TRY(set_dev(h));
-    vlq::ListStore ls = list_store(h);
-    TRY(vlq::lists_sync_host(ls, h->stream));
-    const int64_t o = h->h_list_off[(size_t)list_id], len = h->h_list_len[(size_t)list_id];
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (len > 0 && out)
-        HIP_TRY(hipMemcpy(out, h->rcodes.as<uint8_t>() + (size_t)o * h->Mr, (size_t)len * h->Mr, hipMemcpyDeviceToHost));
-    return VLQ_OK;
+    return vlq::lists_read(h->lists, list_id, nullptr, out, nullptr, h->stream);
 }
 
 int vlq_ivfpq_refine(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* shortlist, int k_coarse, int k, float* D, int64_t* I) {

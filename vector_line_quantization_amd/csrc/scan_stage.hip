@@ -100,9 +100,9 @@ bool ensure_code_sums(vlq_ivfpq_t h) {
         (void)hipMemsetAsync(h->sums_cnt.p, 0, 16, h->stream);
     }
     // one float per slot the code array holds (its capacity bounds every list's end)
-    if (!quiet(h->code_sums.reserve((h->codes.cap / (size_t)h->M + 1) * sizeof(float)))) return false;
+    if (!quiet(h->code_sums.reserve((h->lists.codes.cap / (size_t)h->M + 1) * sizeof(float)))) return false;
     if (!quiet(h->t2abs.reserve((size_t)h->nlist * sizeof(float)))) return false;
-    vlq::launch_code_sums(h->codes.as<uint8_t>(), h->list_off.as<int64_t>(), h->list_len.as<int64_t>(), h->nlist, h->term2.as<float>(),
+    vlq::launch_code_sums(h->lists.codes.as<uint8_t>(), h->lists.off.as<int64_t>(), h->lists.len.as<int64_t>(), h->nlist, h->term2.as<float>(),
                           h->code_sums.as<float>(), h->t2abs.as<float>(), h->stream);
     if (hipGetLastError() != hipSuccess) return false;
     h->sums_valid = true;
@@ -138,8 +138,8 @@ static int ensure_term2h(vlq_ivfpq_t h) {
 static vlq::ScanArgs page_args(vlq_ivfpq_t h, int64_t i0, int64_t ni, const float* x_dev, const int64_t* keys_dev, const float* cdis_dev,
                                int nprobe, int k, float* D_dev, int64_t* I_dev, int store_pairs) {
     vlq::ScanArgs a;
-    a.codes = h->codes.as<uint8_t>(); a.ids = h->ids.as<int64_t>();
-    a.list_off = h->list_off.as<int64_t>(); a.list_len = h->list_len.as<int64_t>();
+    a.codes = h->lists.codes.as<uint8_t>(); a.ids = h->lists.ids.as<int64_t>();
+    a.list_off = h->lists.off.as<int64_t>(); a.list_len = h->lists.len.as<int64_t>();
     a.term2 = nullptr; a.qtab = nullptr; a.table_mode = 0;      // (the caller's)
     a.coarse = h->coarse.as<float>(); a.pq_cent = h->pq.as<float>(); a.pq_cent_t = h->pq_t.as<float>();
     a.queries = x_dev + i0 * h->d;
@@ -318,7 +318,7 @@ static int scan_dev(vlq_ivfpq_t h, int64_t n, const float* x_dev, const int64_t*
                                         nullptr, nullptr, vlq::WalkSeed(), true, false, lpart, h->ws_qkey.as<uint32_t>());
             } else {
                 vlq::WalkSeed wseed;
-                wseed.list_off = h->list_off.as<int64_t>(); wseed.list_len = h->list_len.as<int64_t>(); wseed.nlist = h->nlist;
+                wseed.list_off = h->lists.off.as<int64_t>(); wseed.list_len = h->lists.len.as<int64_t>(); wseed.nlist = h->nlist;
                 wseed.slots = plan.walk_seed_slots;
                 int* counts = walk_auto ? h->walk_counts.as<int>() : nullptr;
                 vlq::launch_query_order(a.keys, ni, nprobe, h->nlist, h->ws_hist.as<int>(), h->ws_qorder.as<int>(), h->stream, rank,

@@ -358,12 +358,111 @@ class GpuIVFPQ:
         return {"coarse_ms": ms[0], "tables_ms": ms[1], "scan_ms": ms[2], "scan_calls": calls.value}
 
 
-class GpuIVFFlat:
+class _GpuIVF:
+    """What GpuIVFFlat and GpuIVFSQ share: the calls of the C ABI that differ in their prefix only (_KIND)."""
+
+    METRICS = GpuIVFPQ.METRICS
+    _KIND = None
+    _out = GpuIVFPQ._out
+
+    def _call(self, name, *args):
+        check(getattr(lib(), self._KIND + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._KIND + "destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # --- state ------------------------------------------------------------
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_coarse_centroids(self, c):
+        p, _k = _ptr(c, np.float32)
+        self._call("set_coarse_centroids", p)
+
+    def _set_lists(self, rows, np_dtype, ids, list_offsets):
+        pv, _a = _ptr(rows, np_dtype)
+        pi, _b = _ptr(ids, np.int64)
+        po, _c = _ptr(list_offsets, np.int64)
+        self._call("set_lists", pv, pi, po)
+
+    @property
+    def ntotal(self):
+        return int(getattr(lib(), self._KIND + "ntotal")(self._h))
+
+    def list_length(self, i):
+        n = C.c_int64()
+        self._call("list_length", C.c_int(i), C.byref(n))
+        return n.value
+
+    def _get_list(self, i, width, np_dtype):
+        rows = np.empty((self.list_length(i), width), np_dtype)
+        ids = np.empty((rows.shape[0],), np.int64)
+        self._call("get_list", C.c_int(i), rows.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p))
+        return rows, ids
+
+    def reset(self):
+        self._call("reset")
+
+    # --- add --------------------------------------------------------------
+    def add(self, x, xids=None):
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        self._call("add", C.c_int64(x.shape[0]), px, pi)
+
+    def add_preassigned(self, x, assign, xids=None):
+        px, _a = _ptr(x, np.float32)
+        pi, _b = _ptr(xids, np.int64)
+        pa, _c = _ptr(assign, np.int64)
+        self._call("add_preassigned", C.c_int64(x.shape[0]), px, pi, pa)
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    def reclaim_memory(self):
+        n = C.c_uint64()
+        self._call("reclaim_memory", C.byref(n))
+        return n.value
+
+    # --- search -----------------------------------------------------------
+    def _rows_out(self, x, width, D, I):
+        """the two outputs of a search of x, [n][width] float32 and int64, with their pointers"""
+        D = self._out(D, (x.shape[0], width), np.float32, x)
+        I = self._out(I, (x.shape[0], width), np.int64, x)
+        return D, I, _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0]
+
+    def search(self, x, nprobe, k, D=None, I=None):
+        px, _a = _ptr(x, np.float32)
+        D, I, pD, pI = self._rows_out(x, k, D, I)
+        self._call("search", C.c_int64(x.shape[0]), px, C.c_int(nprobe), C.c_int(k), pD, pI)
+        return D, I
+
+    def coarse_search(self, x, nprobe, cdis=None, keys=None):
+        px, _a = _ptr(x, np.float32)
+        cdis, keys, pc, pk = self._rows_out(x, nprobe, cdis, keys)
+        self._call("coarse_search", C.c_int64(x.shape[0]), px, C.c_int(nprobe), pc, pk)
+        return cdis, keys
+
+    # --- introspection ----------------------------------------------------
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
+class GpuIVFFlat(_GpuIVF):
     """faiss::IndexIVFFlat / gpu::GpuIndexIVFFlat (IndexIVF.h:132-205, gpu/GpuIndexIVFFlat.h): inverted lists of the vectors
     themselves, exact distances.  metric "l2": ascending squared distances, FLT_MAX / -1 padding; "ip": descending inner
     products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfflat_*)."""
 
-    METRICS = GpuIVFPQ.METRICS
+    _KIND = "vlq_ivfflat_"
 
     def __init__(self, d, nlist, device=0, metric="l2"):
         self.d, self.nlist, self.device = d, nlist, device
@@ -373,127 +472,42 @@ class GpuIVFFlat:
         self.metric = metric
         check(lib().vlq_ivfflat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist), C.c_int(self.METRICS[metric])))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_ivfflat_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    _out = GpuIVFPQ._out
-
-    # --- state ------------------------------------------------------------
-    def set_stream(self, stream_ptr):
-        check(lib().vlq_ivfflat_set_stream(self._h, C.c_void_p(stream_ptr or 0)))
-
-    def set_coarse_centroids(self, c):
-        p, _k = _ptr(c, np.float32)
-        check(lib().vlq_ivfflat_set_coarse_centroids(self._h, p))
-
     def set_lists(self, vecs, ids, list_offsets):
         """vecs [ntotal][d] float32 and ids [ntotal] in list-contiguous order, list_offsets [nlist + 1]"""
-        pv, _a = _ptr(vecs, np.float32)
-        pi, _b = _ptr(ids, np.int64)
-        po, _c = _ptr(list_offsets, np.int64)
-        check(lib().vlq_ivfflat_set_lists(self._h, pv, pi, po))
-
-    @property
-    def ntotal(self):
-        return int(lib().vlq_ivfflat_ntotal(self._h))
-
-    def list_length(self, i):
-        n = C.c_int64()
-        check(lib().vlq_ivfflat_list_length(self._h, C.c_int(i), C.byref(n)))
-        return n.value
+        self._set_lists(vecs, np.float32, ids, list_offsets)
 
     def get_list(self, i):
-        n = self.list_length(i)
-        vecs = np.empty((n, self.d), np.float32)
-        ids = np.empty((n,), np.int64)
-        check(lib().vlq_ivfflat_get_list(self._h, C.c_int(i), vecs.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
-        return vecs, ids
-
-    def reset(self):
-        check(lib().vlq_ivfflat_reset(self._h))
-
-    # --- add --------------------------------------------------------------
-    def add(self, x, xids=None):
-        px, _a = _ptr(x, np.float32)
-        pi, _b = _ptr(xids, np.int64)
-        check(lib().vlq_ivfflat_add(self._h, C.c_int64(x.shape[0]), px, pi))
+        return self._get_list(i, self.d, np.float32)
 
     def add_preassigned(self, x, assign, xids=None):
         """IndexIVFFlat::add_core with precomputed_idx: a negative list id drops the vector"""
-        px, _a = _ptr(x, np.float32)
-        pi, _b = _ptr(xids, np.int64)
-        pa, _c = _ptr(assign, np.int64)
-        check(lib().vlq_ivfflat_add_preassigned(self._h, C.c_int64(x.shape[0]), px, pi, pa))
-
-    def reserve_memory(self, num_vecs):
-        check(lib().vlq_ivfflat_reserve_memory(self._h, C.c_int64(num_vecs)))
-
-    def reclaim_memory(self):
-        n = C.c_uint64()
-        check(lib().vlq_ivfflat_reclaim_memory(self._h, C.byref(n)))
-        return n.value
-
-    # --- search -----------------------------------------------------------
-    def search(self, x, nprobe, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        pD, _b = _out_ptr(D, np.float32)
-        pI, _c = _out_ptr(I, np.int64)
-        check(lib().vlq_ivfflat_search(self._h, C.c_int64(n), px, C.c_int(nprobe), C.c_int(k), pD, pI))
-        return D, I
+        super().add_preassigned(x, assign, xids)
 
     def search_preassigned(self, x, keys, k, D=None, I=None):
-        n, nprobe = x.shape[0], keys.shape[1]
         px, _a = _ptr(x, np.float32)
         pk, _b = _ptr(keys, np.int64)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        pD, _d = _out_ptr(D, np.float32)
-        pI, _e = _out_ptr(I, np.int64)
-        check(lib().vlq_ivfflat_search_preassigned(self._h, C.c_int64(n), px, pk, C.c_int(nprobe), C.c_int(k), pD, pI))
+        D, I, pD, pI = self._rows_out(x, k, D, I)
+        self._call("search_preassigned", C.c_int64(x.shape[0]), px, pk, C.c_int(keys.shape[1]), C.c_int(k), pD, pI)
         return D, I
 
-    def coarse_search(self, x, nprobe, cdis=None, keys=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        cdis = self._out(cdis, (n, nprobe), np.float32, x)
-        keys = self._out(keys, (n, nprobe), np.int64, x)
-        pc, _b = _out_ptr(cdis, np.float32)
-        pk, _c = _out_ptr(keys, np.int64)
-        check(lib().vlq_ivfflat_coarse_search(self._h, C.c_int64(n), px, C.c_int(nprobe), pc, pk))
-        return cdis, keys
-
-    # --- introspection ----------------------------------------------------
     def stats(self, reset=False):
         """IndexIVFFlatStats since the last reset: (nq, lists visited, distances computed)"""
         nq, nl, nd = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        check(lib().vlq_ivfflat_stats(self._h, C.byref(nq), C.byref(nl), C.byref(nd), C.c_int(int(reset))))
+        self._call("stats", C.byref(nq), C.byref(nl), C.byref(nd), C.c_int(int(reset)))
         return nq.value, nl.value, nd.value
 
     def last_scan_info(self):
         """the kernel instantiation and read path of the last list scan (include/vlq_ivfpq.h)"""
-        buf = C.create_string_buffer(256)
-        check(lib().vlq_ivfflat_last_scan_info(self._h, buf, C.c_int(256)))
-        return buf.value.decode()
+        return super().last_scan_info()
 
 
-class GpuIVFSQ:
+class GpuIVFSQ(_GpuIVF):
     """faiss::IndexIVFScalarQuantizer (IndexScalarQuantizer.h:129-155; "IVFx,SQ8" / "IVFx,SQ4" of index_factory): inverted
     lists of 8- or 4-bit codes per component of the residual.  qtype: "8bit", "4bit", "8bit_uniform", "4bit_uniform" (or
     ScalarQuantizer::QuantizerType's number).  metric "l2": ascending distances, FLT_MAX / -1 padding; "ip": descending inner
     products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfsq_*)."""
 
-    METRICS = GpuIVFPQ.METRICS
+    _KIND = "vlq_ivfsq_"
     QTYPES = {"8bit": 0, "4bit": 1, "8bit_uniform": 2, "4bit_uniform": 3}      # ScalarQuantizer::QuantizerType
 
     def __init__(self, d, nlist, qtype, device=0, metric="l2"):
@@ -511,26 +525,8 @@ class GpuIVFSQ:
                                      C.c_int(self.METRICS[metric])))
         self.code_size = int(lib().vlq_ivfsq_code_size(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_ivfsq_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    _out = GpuIVFPQ._out
-
-    # --- state ------------------------------------------------------------
-    def set_stream(self, stream_ptr):
-        check(lib().vlq_ivfsq_set_stream(self._h, C.c_void_p(stream_ptr or 0)))
-
     def set_coarse_centroids(self, c):
-        p, _k = _ptr(c, np.float32)
-        check(lib().vlq_ivfsq_set_coarse_centroids(self._h, p))
+        super().set_coarse_centroids(c)
         # train() takes the residuals on the host
         host = c.detach().cpu().numpy() if _is_torch(c) else c
         self._centroids = np.array(host, dtype=np.float32).reshape(self.nlist, self.d)
@@ -538,12 +534,12 @@ class GpuIVFSQ:
     def set_trained(self, trained):
         """ScalarQuantizer::trained: vmin[d] then vdiff[d] (two floats for the uniform types), host floats"""
         t = np.ascontiguousarray(np.asarray(trained, dtype=np.float32).ravel())
-        check(lib().vlq_ivfsq_set_trained(self._h, t.ctypes.data_as(C.c_void_p), C.c_int(t.size)))
+        self._call("set_trained", t.ctypes.data_as(C.c_void_p), C.c_int(t.size))
 
     @property
     def trained(self):
         t = np.empty(2 if self.uniform else 2 * self.d, np.float32)
-        check(lib().vlq_ivfsq_get_trained(self._h, t.ctypes.data_as(C.c_void_p), C.c_int(t.size)))
+        self._call("get_trained", t.ctypes.data_as(C.c_void_p), C.c_int(t.size))
         return t
 
     def train(self, x):
@@ -564,42 +560,14 @@ class GpuIVFSQ:
 
     def set_lists(self, codes, ids, list_offsets):
         """codes [ntotal][code_size] uint8 and ids [ntotal] in list-contiguous order, list_offsets [nlist + 1]"""
-        pv, _a = _ptr(codes, np.uint8)
-        pi, _b = _ptr(ids, np.int64)
-        po, _c = _ptr(list_offsets, np.int64)
-        check(lib().vlq_ivfsq_set_lists(self._h, pv, pi, po))
-
-    @property
-    def ntotal(self):
-        return int(lib().vlq_ivfsq_ntotal(self._h))
-
-    def list_length(self, i):
-        n = C.c_int64()
-        check(lib().vlq_ivfsq_list_length(self._h, C.c_int(i), C.byref(n)))
-        return n.value
+        self._set_lists(codes, np.uint8, ids, list_offsets)
 
     def get_list(self, i):
-        n = self.list_length(i)
-        codes = np.empty((n, self.code_size), np.uint8)
-        ids = np.empty((n,), np.int64)
-        check(lib().vlq_ivfsq_get_list(self._h, C.c_int(i), codes.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
-        return codes, ids
-
-    def reset(self):
-        check(lib().vlq_ivfsq_reset(self._h))
-
-    # --- add --------------------------------------------------------------
-    def add(self, x, xids=None):
-        px, _a = _ptr(x, np.float32)
-        pi, _b = _ptr(xids, np.int64)
-        check(lib().vlq_ivfsq_add(self._h, C.c_int64(x.shape[0]), px, pi))
+        return self._get_list(i, self.code_size, np.uint8)
 
     def add_preassigned(self, x, assign, xids=None):
         """add_with_ids behind a given assignment: a negative list id drops the vector"""
-        px, _a = _ptr(x, np.float32)
-        pi, _b = _ptr(xids, np.int64)
-        pa, _c = _ptr(assign, np.int64)
-        check(lib().vlq_ivfsq_add_preassigned(self._h, C.c_int64(x.shape[0]), px, pi, pa))
+        super().add_preassigned(x, assign, xids)
 
     def encode(self, x):
         """(codes [n][code_size], assignment [n]) that add would store; nothing is stored"""
@@ -607,57 +575,21 @@ class GpuIVFSQ:
         px, _a = _ptr(x, np.float32)
         codes = np.empty((n, self.code_size), np.uint8)
         assign = np.empty((n,), np.int64)
-        check(lib().vlq_ivfsq_encode(self._h, C.c_int64(n), px, codes.ctypes.data_as(C.c_void_p), assign.ctypes.data_as(C.c_void_p)))
+        self._call("encode", C.c_int64(n), px, codes.ctypes.data_as(C.c_void_p), assign.ctypes.data_as(C.c_void_p))
         return codes, assign
-
-    def reserve_memory(self, num_vecs):
-        check(lib().vlq_ivfsq_reserve_memory(self._h, C.c_int64(num_vecs)))
-
-    def reclaim_memory(self):
-        n = C.c_uint64()
-        check(lib().vlq_ivfsq_reclaim_memory(self._h, C.byref(n)))
-        return n.value
-
-    # --- search -----------------------------------------------------------
-    def search(self, x, nprobe, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        pD, _b = _out_ptr(D, np.float32)
-        pI, _c = _out_ptr(I, np.int64)
-        check(lib().vlq_ivfsq_search(self._h, C.c_int64(n), px, C.c_int(nprobe), C.c_int(k), pD, pI))
-        return D, I
 
     def search_preassigned(self, x, keys, coarse_dis, k, D=None, I=None):
         """coarse_dis [n][nprobe] is read under inner product only and may be None for L2"""
-        n, nprobe = x.shape[0], keys.shape[1]
         px, _a = _ptr(x, np.float32)
         pk, _b = _ptr(keys, np.int64)
         pc, _f = _ptr(coarse_dis, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        pD, _d = _out_ptr(D, np.float32)
-        pI, _e = _out_ptr(I, np.int64)
-        check(lib().vlq_ivfsq_search_preassigned(self._h, C.c_int64(n), px, pk, pc, C.c_int(nprobe), C.c_int(k), pD, pI))
+        D, I, pD, pI = self._rows_out(x, k, D, I)
+        self._call("search_preassigned", C.c_int64(x.shape[0]), px, pk, pc, C.c_int(keys.shape[1]), C.c_int(k), pD, pI)
         return D, I
 
-    def coarse_search(self, x, nprobe, cdis=None, keys=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        cdis = self._out(cdis, (n, nprobe), np.float32, x)
-        keys = self._out(keys, (n, nprobe), np.int64, x)
-        pc, _b = _out_ptr(cdis, np.float32)
-        pk, _c = _out_ptr(keys, np.int64)
-        check(lib().vlq_ivfsq_coarse_search(self._h, C.c_int64(n), px, C.c_int(nprobe), pc, pk))
-        return cdis, keys
-
-    # --- introspection ----------------------------------------------------
     def last_scan_info(self):
         """the kernel instantiation and read path of the last list scan (include/vlq_ivfpq.h); raises a pending bad-key error"""
-        buf = C.create_string_buffer(256)
-        check(lib().vlq_ivfsq_last_scan_info(self._h, buf, C.c_int(256)))
-        return buf.value.decode()
+        return super().last_scan_info()
 
 
 class GpuVLQ:
