@@ -95,8 +95,8 @@ inline IndexIVFFlatStats indexIVFFlat_stats;   // "global var that collects them
 /// faiss::IndexIVFFlat (IndexIVF.h:132-205, IndexIVF.cpp:200-582): the inverted lists hold the vectors themselves.  Same public
 /// data model (ids / vecs per list); the host-side lists stay the authoritative copy -- what write_index and copyFrom read --
 /// and are mirrored to the device list-contiguously before the first search after a change.  add_core assigns on the device
-/// (the quantizer's 1-NN) and appends to the host lists; search and search_preassigned run on the device (vlq_ivfflat_*).
-/// range_search, update_vectors and IndexIVFFlatIPBounds are not built.
+/// (the quantizer's 1-NN) and appends to the host lists; search, search_preassigned and range_search run on the device
+/// (vlq_ivfflat_*).  update_vectors and IndexIVFFlatIPBounds are not built.
 struct IndexIVFFlat : IndexIVF {
   std::vector<std::vector<float> > vecs;   ///< list i: an nl x d matrix
 
@@ -153,6 +153,20 @@ struct IndexIVFFlat : IndexIVF {
     sync_();
     VLQ_CHECK(vlq_ivfflat_search_preassigned(h_, n, x, (const int64_t*)assign, (int)nprobe, (int)k, distances, (int64_t*)labels));
     collect_stats_();
+  }
+
+  /// IndexIVF.cpp:401-449: quantizer->assign with nprobe, then every stored vector of those lists with dis < radius (L2) or
+  /// ip > radius (inner product), per query in scan order (probe order, then list position) -- one device call.  The counts go
+  /// through result->do_allocation() as in the reference, so an overloaded allocation is honoured.  indexIVFFlat_stats is
+  /// not touched (the reference's range_search keeps no statistics).
+  void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override {
+    FAISS_THROW_IF_NOT_MSG(result && (idx_t)result->nq == n, "RangeSearchResult must be constructed for the n queries");
+    sync_();
+    std::vector<int64_t> lims((size_t)n + 1, 0);
+    VLQ_CHECK(vlq_ivfflat_range_search(h_, n, x, (int)nprobe, radius, lims.data(), nullptr));
+    for (idx_t i = 0; i < n; i++) result->lims[i] = (size_t)(lims[i + 1] - lims[i]);
+    result->do_allocation();
+    VLQ_CHECK(vlq_ivfflat_range_result(h_, result->distances, (int64_t*)result->labels));
   }
 
   void reset() override {   // IndexIVF.cpp:533-539

@@ -362,7 +362,14 @@ int vlq_ivfpq_profile_read(vlq_ivfpq_t h, double ms[3], int64_t* calls, int rese
  * call with a host D or I, from the next vlq_ivfflat_stats() otherwise).
  * Limits: k <= VLQ_MAX_K, nprobe <= VLQ_MAX_NPROBE, 4 * d + 24 * nprobe within the kernel's LDS (d up to about 29 000):
  * VLQ_ERR_UNSUPPORTED otherwise, there is no other path.  float16 storage (GpuIndexIVFFlatConfig::useFloat16IVFStorage),
- * range_search, update_vectors and the direct map are not built.
+ * update_vectors and the direct map are not built.
+ * Range search (IndexIVFFlat::range_search, IndexIVF.cpp:401-449; csrc/scan_range_flat.hip): every stored vector of the
+ * probed lists with dis < radius (L2) or ip > radius (inner product) -- both strict, a NaN radius or distance is no hit --
+ * with the same distance bits as the k-NN scan.  The hits of a query stand in scan order: the probes in the order given,
+ * the rows of a list in stored order (what the reference writes, whatever its thread count).  A key < 0 OR >= nlist makes
+ * the call fail with VLQ_ERR_INVALID (the reference aborts, :421-425), for host and device outputs alike, and leaves an
+ * empty result; there is no k, no max_codes and no cap on the hits, and IndexIVFFlatStats is not touched.  Limits: nprobe
+ * <= VLQ_MAX_NPROBE and the same LDS bound.  The call synchronises the stream once (it reads the number of hits).
  * Pointers marked [h|d] as above. */
 typedef struct vlq_ivfflat_s* vlq_ivfflat_t;
 
@@ -400,11 +407,22 @@ int vlq_ivfflat_search(vlq_ivfflat_t h, int64_t n, const float* x, int nprobe, i
 /* IndexIVFFlat::search_preassigned (IndexIVF.cpp:383-398): keys[n*nprobe] [h|d] */
 int vlq_ivfflat_search_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, int k,
                                    float* D, int64_t* I);
+/* IndexIVFFlat::range_search (IndexIVF.cpp:401-449).  lims[n+1] [h|d]; *total = lims[n] (host, may be NULL).
+ * The hits stay in the handle until the next range search, reset or destroy.  Every range search call drops the previous hits
+ * before it looks at its arguments: after a call that failed, for whatever reason, the handle holds an empty result. */
+int vlq_ivfflat_range_search(vlq_ivfflat_t h, int64_t n, const float* x, int nprobe, float radius, int64_t* lims, int64_t* total);
+/* the same from the caller's probes: keys[n*nprobe] [h|d]; a key < 0 or >= nlist: VLQ_ERR_INVALID (the reference aborts) */
+int vlq_ivfflat_range_search_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, float radius,
+                                         int64_t* lims, int64_t* total);
+/* RangeSearchResult::distances / labels of the last range search: D[total], I[total] [h|d], either may be NULL; may be called
+ * again */
+int vlq_ivfflat_range_result(vlq_ivfflat_t h, float* D, int64_t* I);
 /* IndexIVFFlatStats (IndexIVF.h:111-119; IndexIVF.cpp:317-319, :367-369) since the last reset: queries, lists visited (empty
  * ones included), distances computed.  Synchronises the stream; raises a pending bad-key error. */
 int vlq_ivfflat_stats(vlq_ivfflat_t h, uint64_t* nq, uint64_t* nlist_visited, uint64_t* ndis, int reset);
 /* Introspection, speed only: the kernel instantiation and read path of the last scan, as text:
- *   "kernel=scan_flat_kernel<1, L2> read=tile128 lds=40304".  Synchronises the stream. */
+ *   "kernel=scan_flat_kernel<1, L2> read=tile128 lds=40304"; after a range search
+ *   "kernel=range_flat_kernel<L2> read=tile128 lds=37152".  Synchronises the stream. */
 int vlq_ivfflat_last_scan_info(vlq_ivfflat_t h, char* buf, int cap);
 
 /* ---- IVF scalar quantizer: inverted lists of 8- or 4-bit codes per component of the residual

@@ -29,6 +29,7 @@ SYMBOLS = [
     "vlq_ivfflat_reclaim_memory", "vlq_ivfflat_ntotal", "vlq_ivfflat_list_length", "vlq_ivfflat_get_list", "vlq_ivfflat_reset",
     "vlq_ivfflat_coarse_search", "vlq_ivfflat_search", "vlq_ivfflat_search_preassigned", "vlq_ivfflat_stats",
     "vlq_ivfflat_last_scan_info",
+    "vlq_ivfflat_range_search", "vlq_ivfflat_range_search_preassigned", "vlq_ivfflat_range_result",
     # IVF scalar quantizer (vlq_ivfsq_t)
     "vlq_ivfsq_create", "vlq_ivfsq_destroy", "vlq_ivfsq_set_stream", "vlq_ivfsq_set_coarse_centroids", "vlq_ivfsq_set_trained",
     "vlq_ivfsq_get_trained", "vlq_ivfsq_code_size", "vlq_ivfsq_set_lists", "vlq_ivfsq_add", "vlq_ivfsq_add_preassigned", "vlq_ivfsq_encode",

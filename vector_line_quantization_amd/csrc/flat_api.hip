@@ -4,9 +4,32 @@
 // index's statistics.
 #include "flat_plan.h"
 #include "ivf_shell.h"
+#include "range_plan.h"
+
+namespace {
+
+// RangeSearchResult::distances / labels of the last range search: blocks of exactly 4 * total and 8 * total bytes
+struct RangeHits {
+    float* D = nullptr;
+    int64_t* I = nullptr;
+    int64_t total = 0;
+    RangeHits() = default;
+    RangeHits(const RangeHits&) = delete;
+    RangeHits& operator=(const RangeHits&) = delete;
+    ~RangeHits() { drop(); }
+    void drop() {
+        if (D) (void)hipFree(D);
+        if (I) (void)hipFree(I);
+        D = nullptr; I = nullptr; total = 0;
+    }
+};
+
+}  // namespace
 
 struct vlq_ivfflat_s : IvfShell {      // stats: [0] distances computed (u64), [1] bad key flag (int), [2] lists visited (u64)
     uint64_t stat_nq = 0;
+    RangeHits range;                   // held until the next range search, reset or destroy
+    DevBuf range_flag, ws_lims, ws_scan;   // the range scan's own bad-key flag (int); lims of a host caller; rocPRIM's storage
 };
 
 namespace {
@@ -48,6 +71,96 @@ int flat_add(vlq_ivfflat_t f, int64_t n, const float* x, const int64_t* xids, co
         TRY(ivf_assign(f, n, xd, &ad));
         return ivf_append(f, n, ad, reinterpret_cast<const uint8_t*>(xd), idd);
     });
+}
+
+const char* const kRangeBadKey = "a probe key < 0 or >= nlist was passed to range_search (IndexIVF.cpp:421-425)";
+
+int range_args(vlq_ivfflat_t f, int64_t n, const void* x, int nprobe, const void* lims) {
+    if (n < 0) return fail(VLQ_ERR_INVALID, "n < 0");
+    if (!lims || (n > 0 && !x)) return fail(VLQ_ERR_INVALID, "null buffer");
+    if (nprobe < 1) return fail(VLQ_ERR_INVALID, "nprobe=%d must be positive", nprobe);
+    if (nprobe > VLQ_MAX_NPROBE) return fail(VLQ_ERR_UNSUPPORTED, "nprobe=%d beyond %d", nprobe, VLQ_MAX_NPROBE);
+    if (n > vlq::kRangeMaxQueries) return fail(VLQ_ERR_UNSUPPORTED, "n=%lld beyond %lld queries of one range search", (long long)n, vlq::kRangeMaxQueries);
+    if (!vlq::plan_flat_range(f->d, nprobe).ok)
+        return fail(VLQ_ERR_UNSUPPORTED, "IVFFlat range scan of d=%d with nprobe=%d does not fit the kernel's LDS", f->d, nprobe);
+    return VLQ_OK;
+}
+
+// Every range search begins here, before any argument is looked at: the hits of the last one go, so that a call that is
+// refused -- for whatever reason -- leaves an empty result in the handle, never the previous call's.
+int range_begin(vlq_ivfflat_t f) {
+    if (!f) return fail(VLQ_ERR_INVALID, "null handle");
+    TRY(set_dev(f->cq));
+    f->range.drop();
+    return VLQ_OK;
+}
+
+// a call without queries: lims[0] = 0, an empty result
+int range_empty(vlq_ivfflat_t f, int64_t* lims, int64_t* total) {
+    if (is_device_ptr(lims)) HIP_TRY(hipMemsetAsync(lims, 0, 8, f->cq->stream));
+    else lims[0] = 0;
+    if (total) *total = 0;
+    return VLQ_OK;
+}
+
+// IndexIVFFlat::range_search behind quantizer->assign, on device buffers: the count pass, the limits, the blocks of exactly
+// `total` hits, the fill pass.  The call synchronises between the passes (it reads lims[n] and the bad-key flag); the
+// statistic counters are not touched (the reference's range_search keeps none).
+int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* kd, int nprobe, float radius, int64_t* lims, int64_t* total) {
+    hipStream_t s = f->cq->stream;
+    const vlq::RangePlan P = vlq::plan_flat_range(f->d, nprobe);
+    const bool dev_lims = is_device_ptr(lims);
+    int64_t* ld = lims;
+    if (!dev_lims) {
+        TRY(f->ws_lims.reserve((size_t)(n + 1) * 8));
+        ld = f->ws_lims.as<int64_t>();
+    }
+    TRY(f->range_flag.reserve(sizeof(int)));
+    vlq::ScanArgs a = {};
+    a.codes = f->lists.codes.as<uint8_t>();
+    a.ids = f->lists.ids.as<int64_t>();
+    a.list_off = f->lists.off.as<int64_t>();
+    a.list_len = f->lists.len.as<int64_t>();
+    a.queries = xd;
+    a.keys = kd;
+    a.bad_key = f->range_flag.as<int>();
+    a.nq = n; a.nprobe = nprobe; a.d = f->d; a.nlist = f->nlist;
+    const bool ip = f->metric == 0;
+    HIP_TRY(hipMemsetAsync(a.bad_key, 0, sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(ld, 0, 8, s));
+    if (!vlq::launch_range_flat(a, ip, radius, ld, false, s))
+        return fail(VLQ_ERR_UNSUPPORTED, "IVFFlat range scan of d=%d with nprobe=%d is not built", f->d, nprobe);
+    HIP_TRY(hipGetLastError());
+    size_t scan_bytes = 0;
+    HIP_TRY(vlq::range_lims_scan(ld + 1, n, nullptr, &scan_bytes, s));
+    TRY(f->ws_scan.reserve(std::max(scan_bytes, (size_t)16)));
+    HIP_TRY(vlq::range_lims_scan(ld + 1, n, f->ws_scan.p, &scan_bytes, s));
+    int64_t tot = 0;
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, ld + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&bad, a.bad_key, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    snprintf(f->last_scan, sizeof(f->last_scan), "kernel=range_flat_kernel<%s> read=%s lds=%zu", ip ? "IP" : "L2", vlq::flat_read_name(P.read),
+             P.lay.bytes);
+    if (bad) return fail(VLQ_ERR_INVALID, "%s", kRangeBadKey);
+    if (tot > 0) {
+        if (hipMalloc((void**)&f->range.D, (size_t)tot * 4) != hipSuccess || hipMalloc((void**)&f->range.I, (size_t)tot * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            f->range.drop();
+            return fail(VLQ_ERR_INVALID, "out of memory (%lld hits of a range search)", (long long)tot);
+        }
+        f->range.total = tot;
+        a.D = f->range.D;
+        a.I = f->range.I;
+        (void)vlq::launch_range_flat(a, ip, radius, ld, true, s);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!dev_lims) {
+        HIP_TRY(hipMemcpyAsync(lims, ld, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (total) *total = tot;
+    return VLQ_OK;
 }
 
 }  // namespace
@@ -92,7 +205,11 @@ int vlq_ivfflat_reclaim_memory(vlq_ivfflat_t f, uint64_t* bytes_reclaimed) { ret
 int64_t vlq_ivfflat_ntotal(vlq_ivfflat_t f) { return f ? f->ntotal : -1; }
 int vlq_ivfflat_list_length(vlq_ivfflat_t f, int list_id, int64_t* len) { return ivf_list_length(f, list_id, len); }
 int vlq_ivfflat_get_list(vlq_ivfflat_t f, int list_id, float* vecs_out, int64_t* ids_out) { return ivf_get_list(f, list_id, vecs_out, ids_out); }
-int vlq_ivfflat_reset(vlq_ivfflat_t f) { return ivf_reset(f); }
+int vlq_ivfflat_reset(vlq_ivfflat_t f) {
+    TRY(ivf_reset(f));
+    f->range.drop();
+    return VLQ_OK;
+}
 
 int vlq_ivfflat_coarse_search(vlq_ivfflat_t f, int64_t n, const float* x, int nprobe, float* cdis, int64_t* keys) {
     return ivf_coarse_search(f, n, x, nprobe, cdis, keys);
@@ -116,6 +233,44 @@ int vlq_ivfflat_search(vlq_ivfflat_t f, int64_t n, const float* x, int nprobe, i
     return ivf_search(f, n, x, nprobe, k, D, I, [&](const float* xd, const int64_t* kd, const float*, float* Dd, int64_t* Id) {
         return flat_scan_dev(f, n, xd, kd, nprobe, k, Dd, Id);
     });
+}
+
+int vlq_ivfflat_range_search_preassigned(vlq_ivfflat_t f, int64_t n, const float* x, const int64_t* keys, int nprobe, float radius,
+                                         int64_t* lims, int64_t* total) {
+    TRY(range_begin(f));
+    TRY(range_args(f, n, x, nprobe, lims));
+    if (n > 0 && !keys) return fail(VLQ_ERR_INVALID, "null keys");
+    if (n == 0) return range_empty(f, lims, total);
+    vlq_ivfpq_t cq = f->cq;
+    const void *xd, *kd;
+    TRY(stage_in(cq, x, (size_t)n * f->d * 4, cq->ws_x, &xd));
+    TRY(stage_in(cq, keys, (size_t)n * nprobe * 8, f->ws_keys_in, &kd));
+    return range_scan_dev(f, n, (const float*)xd, (const int64_t*)kd, nprobe, radius, lims, total);
+}
+
+int vlq_ivfflat_range_search(vlq_ivfflat_t f, int64_t n, const float* x, int nprobe, float radius, int64_t* lims, int64_t* total) {
+    TRY(range_begin(f));
+    TRY(ivf_ready(f));
+    TRY(range_args(f, n, x, nprobe, lims));
+    if (n == 0) return range_empty(f, lims, total);
+    vlq_ivfpq_t cq = f->cq;
+    TRY(cq->ws_keys.reserve((size_t)n * nprobe * 8));
+    TRY(cq->ws_cdis.reserve((size_t)n * nprobe * 4));
+    const void* xd = nullptr;
+    TRY(stage_in(cq, x, (size_t)n * f->d * 4, cq->ws_x, &xd));
+    TRY(coarse_dev(cq, n, (const float*)xd, nprobe, cq->ws_cdis.as<float>(), cq->ws_keys.as<int64_t>()));
+    return range_scan_dev(f, n, (const float*)xd, cq->ws_keys.as<int64_t>(), nprobe, radius, lims, total);
+}
+
+int vlq_ivfflat_range_result(vlq_ivfflat_t f, float* D, int64_t* I) {
+    if (!f) return fail(VLQ_ERR_INVALID, "null handle");
+    if (f->range.total == 0) return VLQ_OK;
+    TRY(set_dev(f->cq));
+    hipStream_t s = f->cq->stream;
+    if (D) HIP_TRY(hipMemcpyAsync(D, f->range.D, (size_t)f->range.total * 4, hipMemcpyDefault, s));
+    if (I) HIP_TRY(hipMemcpyAsync(I, f->range.I, (size_t)f->range.total * 8, hipMemcpyDefault, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VLQ_OK;
 }
 
 int vlq_ivfflat_stats(vlq_ivfflat_t f, uint64_t* nq, uint64_t* nlist_visited, uint64_t* ndis, int reset) {

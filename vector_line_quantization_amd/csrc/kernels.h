@@ -314,6 +314,15 @@ void launch_coarse_ip_finish(float* cdis, const int64_t* keys, int64_t n, hipStr
 // computed), a.bad_key, a.nq, a.nprobe, a.k, a.d, a.nlist are read, nothing else.  nlist_visited: += keys in 0 .. nlist-1.
 // Which instantiation, read path and LDS size serve a shape is plan_flat_scan's decision (flat_plan.h); false: not built.
 bool launch_scan_flat(const ScanArgs& a, bool inner_product, unsigned long long* nlist_visited, hipStream_t s);
+// IndexIVFFlat::range_search's scan (IndexIVF.cpp:401-449; scan_range_flat.hip), one of its two passes: a.codes, a.queries,
+// a.keys, a.ids, a.list_off / a.list_len, a.nq, a.nprobe, a.d, a.nlist are read, no counter is touched.
+//   fill = false  lims[q + 1] = hits of query q (lims[n + 1]); a.bad_key is set if a key < 0 or >= nlist was met
+//   fill = true   lims holds the limits; hit r of query q in scan order goes to a.D / a.I [lims[q] + r]
+// Shape limits are plan_flat_range's (range_plan.h); false: not built.
+bool launch_range_flat(const ScanArgs& a, bool inner_product, float radius, int64_t* lims, bool fill, hipStream_t s);
+// counts to limits, in place: v[i] += v[0] + .. + v[i-1] for the n values at v (rocPRIM's scan).  tmp == nullptr: only
+// *tmp_bytes, the temporary storage the call needs, is set.
+hipError_t range_lims_scan(int64_t* v, int64_t n, void* tmp, size_t* tmp_bytes, hipStream_t s);
 
 // IVF scalar quantizer (IndexIVFScalarQuantizer::search, IndexScalarQuantizer.cpp:884-989; scan_sq.hip): a.codes holds the lists'
 // codes as rows of sq_code_size(d, qtype) bytes; a.queries, a.coarse (the centroids: the L2 residual of every probe), a.keys,

@@ -490,6 +490,42 @@ class GpuIVFFlat(_GpuIVF):
         self._call("search_preassigned", C.c_int64(x.shape[0]), px, pk, C.c_int(keys.shape[1]), C.c_int(k), pD, pI)
         return D, I
 
+    def reset(self):
+        super().reset()
+        self._range_total = 0
+
+    # --- range search -----------------------------------------------------
+    def _range(self, name, x, *args):
+        """(lims [n + 1], D [total], I [total]) of a range search of x: outputs on x's device if x is a device tensor.  The radius
+        goes as a C float: the loader sets no argtypes, and a bare Python float would be passed as a double."""
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        lims = self._out(None, (n + 1,), np.int64, x)
+        total = C.c_int64()
+        self._range_total = 0          # (a failed call leaves an empty result in the handle)
+        self._call(name, C.c_int64(n), px, *args, _out_ptr(lims, np.int64)[0], C.byref(total))
+        self._range_total = total.value
+        return (lims,) + self.range_result(like=x)
+
+    def range_search(self, x, nprobe, radius):
+        """IndexIVFFlat::range_search: every stored vector of the nprobe nearest lists with dis < radius ("l2") or ip > radius
+        ("ip"), per query in scan order (probe order, then list position); query i's hits are D / I [lims[i]:lims[i + 1]]"""
+        return self._range("range_search", x, C.c_int(nprobe), C.c_float(radius))
+
+    def range_search_preassigned(self, x, keys, radius):
+        """the same from the caller's probes keys [n][nprobe]; a key < 0 or >= nlist is an error (the reference aborts)"""
+        pk, _b = _ptr(keys, np.int64)
+        return self._range("range_search_preassigned", x, pk, C.c_int(keys.shape[1]), C.c_float(radius))
+
+    def range_result(self, like=None):
+        """(D, I) of the last range search again (held until the next range search, reset or close); device tensors if
+        `like` is one"""
+        total = getattr(self, "_range_total", 0)
+        D = self._out(None, (total,), np.float32, like)
+        I = self._out(None, (total,), np.int64, like)
+        self._call("range_result", _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
     def stats(self, reset=False):
         """IndexIVFFlatStats since the last reset: (nq, lists visited, distances computed)"""
         nq, nl, nd = C.c_uint64(), C.c_uint64(), C.c_uint64()
