@@ -5,6 +5,7 @@
 //   "IxF2"  IndexFlatL2            "Imiq"  MultiIndexQuantizer        "IvPQ"  IndexIVFPQ
 //   "IvFl"  IndexIVFFlat (index_io.cpp:276-283, :597-603)
 //   "IvSQ"  IndexIVFScalarQuantizer (index_io.cpp:208-215, :283-292, :439-447, :611-620)
+//   "IxPq"  IndexPQ (index_io.cpp:259-270); read as well: its older records "IxPQ" and "IxPo" (:578-596)
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
 // and rejected.
@@ -96,6 +97,14 @@ inline void write_index(const Index* idx, FILE* f) {
     w1(f, fourcc("Imiq"));
     write_header(idx, f);
     write_pq(miq->pq, f);
+  } else if (const IndexPQ* idxp = dynamic_cast<const IndexPQ*>(idx)) {
+    w1(f, fourcc("IxPq"));                     // index_io.cpp:259-270
+    write_header(idx, f);
+    write_pq(idxp->pq, f);
+    wvec(f, idxp->codes);
+    w1(f, idxp->search_type);
+    w1(f, idxp->encode_signs);
+    w1(f, idxp->polysemous_ht);
   } else if (const IndexIVFFlat* ivfl = dynamic_cast<const IndexIVFFlat*>(idx)) {
     w1(f, fourcc("IvFl"));                     // index_io.cpp:276-283
     write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
@@ -167,6 +176,23 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     read_header(miq.get(), f);
     read_pq(miq->pq, f);
     return miq.release();
+  }
+  if (h == fourcc("IxPQ") || h == fourcc("IxPo") || h == fourcc("IxPq")) {      // index_io.cpp:578-596
+    std::unique_ptr<IndexPQ> idxp(new IndexPQ());
+    read_header(idxp.get(), f);
+    read_pq(idxp->pq, f);
+    rvec(f, idxp->codes);
+    if (h == fourcc("IxPo") || h == fourcc("IxPq")) {
+      r1(f, idxp->search_type);
+      r1(f, idxp->encode_signs);
+      r1(f, idxp->polysemous_ht);
+    }
+    // "Old versions of PQ all had metric_type set to INNER_PRODUCT when they were in fact using L2" (:590-595)
+    if (h == fourcc("IxPQ") || h == fourcc("IxPo")) idxp->metric_type = METRIC_L2;
+    FAISS_THROW_IF_NOT(idxp->codes.size() == (size_t)idxp->ntotal * idxp->pq.code_size);
+    idxp->quantizer_changed();
+    idxp->codes_changed();
+    return idxp.release();
   }
   if (h == fourcc("IvFl")) {                   // index_io.cpp:597-603
     std::unique_ptr<IndexIVFFlat> iv(new IndexIVFFlat());

@@ -496,6 +496,72 @@ int vlq_ivfsq_search_preassigned(vlq_ivfsq_t h, int64_t n, const float* x, const
  * pending bad-key error. */
 int vlq_ivfsq_last_scan_info(vlq_ivfsq_t h, char* buf, int cap);
 
+/* ---- Flat PQ index: every stored code is scored for every query (faiss::IndexPQ, IndexPQ.h:28-117, IndexPQ.cpp:54-358; what
+ * index_factory builds for "PQ16", AutoTune.cpp:752-767).  A handle of its own; the scan is csrc/scan_pq.hip under the plan of
+ * csrc/pq_plan.h: a grid of (query tile) x (code slice), the tables of a tile interleaved in LDS, slices joined by the total
+ * order (distance, scan position).  Labels are scan positions 0 .. ntotal-1.
+ *   ST_PQ (0)  L2: compute_distance_tables, max-heap `dis < top`, rows ascending, padding FLT_MAX / -1 (IndexPQ.cpp:130-133).
+ *              Inner product: compute_inner_prod_tables, min-heap, rows descending, padding -FLT_MAX / -1 (:134-137).
+ *              The table entries of a code are added in the order of pq_estimators_from_tables (ProductQuantizer.cpp:46-143):
+ *              M == 4: ((t0 + t1) + t2) + t3; M % 4 == 0: from 0, groups ((t0 + t1) + t2) + t3 added one by one; any other M: from
+ *              0, left to right.  This is NOT the strictly left-to-right sum of the IVFPQ list scan (IndexIVFPQ.cpp:781-802).
+ *   ST_polysemous (4), ST_polysemous_generalize (5)  (IndexPQ.cpp:260-358) L2 only and code_size % 8 == 0, else
+ *              VLQ_ERR_INVALID from the search (the reference throws there).  q_code = compute_code_from_distance_table of the
+ *              query's table (the first minimum, from 1e20: ProductQuantizer.cpp:363-383); a code is looked up only if
+ *              hd < polysemous_ht, hd = popcount of the XOR over the whole code (4) or the number of differing bytes (5,
+ *              generalized_hamming_64); passers are summed from 0, left to right, whatever M is (:242-247).
+ *   ST_SDC (3) (IndexPQ.cpp:168-173, ProductQuantizer.cpp:595-660) the metric is ignored, as in the reference: the query is
+ *              encoded with compute_codes, the distance of a code is sum_m sdc_table[m][b[m] + q[m] * ksub] from 0, left to
+ *              right; sdc_table[m][i + j * ksub] = sum_c (ci[c] - cj[c])^2, a scalar left-to-right sum, built on the device at the
+ *              first ST_SDC search after the centroids changed.
+ *   ST_HE (1), ST_generalized_HE (2) and encode_signs are not built: vlq_pq_set_search_type returns VLQ_ERR_UNSUPPORTED.
+ * Tables and codes with dsub < 16 are the reference's bit for bit (fvec_L2sqr_ny / fvec_inner_products_ny in the SSE order).
+ * With dsub >= 16 the reference takes a BLAS path (ProductQuantizer.cpp:395-406, :452-461, :477-490) whose rounding is not
+ * reproducible; here the tables are computed in the same non-BLAS order as for dsub < 16: equal to the reference's to
+ * rounding, 2 (dsub + 3) 2^-24 (|x_m|^2 + |c_mj|^2) per entry, and the scan over them is exact as stated.
+ * Ties: among equal distances the lower scan position wins, which is the reference's strict admission up to the heap's
+ * history inside a group of exactly equal distances.
+ * Limits: nbits 1..8 (one byte per index; 9..16: VLQ_ERR_UNSUPPORTED), M <= 64 (M % 4 == 0 is read by words, any other M byte
+ * by byte), k <= VLQ_MAX_K, ntotal < 2^32 (the key's position field), the tile's tables and merge area within 160 KB of LDS
+ * (VLQ_ERR_UNSUPPORTED names M, ksub, k).  Pointers marked [h|d] as above. */
+typedef struct vlq_pq_s* vlq_pq_t;
+
+/* IndexPQ::IndexPQ (IndexPQ.cpp:40-51).  metric: 0 = inner product, 1 = L2.  polysemous_ht starts at nbits * M + 1. */
+int vlq_pq_create(vlq_pq_t* out, int device, int d, int M, int nbits, int metric);
+void vlq_pq_destroy(vlq_pq_t h);
+int vlq_pq_set_stream(vlq_pq_t h, void* hip_stream);
+/* ProductQuantizer::centroids: c[M][ksub][dsub] [h|d] */
+int vlq_pq_set_centroids(vlq_pq_t h, const float* centroids);
+/* IndexPQ::codes (index_io.cpp:587): codes[n*M] [h|d]; replaces the stored codes */
+int vlq_pq_set_codes(vlq_pq_t h, const uint8_t* codes, int64_t n);
+/* IndexPQ::add (IndexPQ.cpp:78-84): pq.compute_codes on the device, the first minimum per sub-quantizer.  x[n*d] [h|d] */
+int vlq_pq_add(vlq_pq_t h, int64_t n, const float* x);
+/* pq.compute_codes (ProductQuantizer.cpp:385-407), nothing stored: codes_out[n*M] [h|d] */
+int vlq_pq_encode(vlq_pq_t h, int64_t n, const float* x, uint8_t* codes_out);
+/* codes i0 .. i0+ni-1 in scan order (what IndexPQ::reconstruct_n decodes, IndexPQ.cpp:94-101): out[ni*M] [h|d] */
+int vlq_pq_get_codes(vlq_pq_t h, int64_t i0, int64_t ni, uint8_t* out);
+int64_t vlq_pq_ntotal(vlq_pq_t h);
+/* IndexPQ::reset (IndexPQ.cpp:88-92) */
+int vlq_pq_reset(vlq_pq_t h);
+int vlq_pq_reserve_memory(vlq_pq_t h, int64_t num_vecs);
+/* IndexPQ::search_type and polysemous_ht (IndexPQ.h:75-91), the reference's enum values 0..5 */
+int vlq_pq_set_search_type(vlq_pq_t h, int search_type, int polysemous_ht);
+/* IndexPQ::search (IndexPQ.cpp:124-203).  x[n*d], D[n*k], I[n*k] [h|d] */
+int vlq_pq_search(vlq_pq_t h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* what the scan reads, for parity tests: the queries' tables out[n*M*ksub] [h|d] (compute_distance_tables,
+ * compute_inner_prod_tables, or under ST_SDC the sdc_table rows of the queries' codes), and the queries' codes out[n*M] [h|d]
+ * (compute_code_from_distance_table under the polysemous types, compute_codes under ST_SDC; ST_PQ reads none: VLQ_ERR_STATE) */
+int vlq_pq_query_tables(vlq_pq_t h, int64_t n, const float* x, float* out);
+int vlq_pq_query_codes(vlq_pq_t h, int64_t n, const float* x, uint8_t* out);
+/* IndexPQStats (IndexPQ.h:119-127; IndexPQ.cpp:139-140, :200-201, :353-355) of this handle since the last reset: nq += n,
+ * ncode += n * ntotal, n_hamming_pass += codes that passed the filter.  Synchronises the stream. */
+int vlq_pq_stats(vlq_pq_t h, uint64_t* nq, uint64_t* ncode, uint64_t* n_hamming_pass, int reset);
+/* Speed only, results never depend on it: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides */
+int vlq_pq_set_scan_split(vlq_pq_t h, int query_tile, int slices);
+/* Introspection, speed only: the last scan launch as text,
+ *   "kernel=scan_pq_kernel<4, 1, group4, none, 16> Q=4 S=2 slice=500000 lds=73744 join=1".  Synchronises the stream. */
+int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@ SYMBOLS = [
     "vlq_ivfsq_get_trained", "vlq_ivfsq_code_size", "vlq_ivfsq_set_lists", "vlq_ivfsq_add", "vlq_ivfsq_add_preassigned", "vlq_ivfsq_encode",
     "vlq_ivfsq_reserve_memory", "vlq_ivfsq_reclaim_memory", "vlq_ivfsq_ntotal", "vlq_ivfsq_list_length", "vlq_ivfsq_get_list",
     "vlq_ivfsq_reset", "vlq_ivfsq_coarse_search", "vlq_ivfsq_search", "vlq_ivfsq_search_preassigned", "vlq_ivfsq_last_scan_info",
+    # flat PQ (vlq_pq_t)
+    "vlq_pq_create", "vlq_pq_destroy", "vlq_pq_set_stream", "vlq_pq_set_centroids", "vlq_pq_set_codes", "vlq_pq_add", "vlq_pq_encode",
+    "vlq_pq_get_codes", "vlq_pq_ntotal", "vlq_pq_reset", "vlq_pq_reserve_memory", "vlq_pq_set_search_type", "vlq_pq_search",
+    "vlq_pq_query_tables", "vlq_pq_query_codes", "vlq_pq_stats", "vlq_pq_set_scan_split", "vlq_pq_last_scan_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -102,6 +106,8 @@ def lib():
         L.vlq_ivfflat_destroy.restype = None
         L.vlq_ivfsq_ntotal.restype = C.c_int64
         L.vlq_ivfsq_destroy.restype = None
+        L.vlq_pq_ntotal.restype = C.c_int64
+        L.vlq_pq_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

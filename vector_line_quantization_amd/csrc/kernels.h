@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "pq_plan.h"
 #include "scan_plan.h"
 
 namespace vlq {
@@ -335,6 +336,31 @@ bool launch_scan_sq(const ScanArgs& a, int qtype, bool inner_product, const floa
 // codes[n][code_size]; a vector whose assign is outside 0 .. nlist-1 gets zero bytes
 void launch_sq_encode(const float* x, int64_t n, int d, const float* coarse, const int64_t* assign, int nlist, const float* trained,
                       int qtype, uint8_t* codes, hipStream_t s);
+
+// Flat PQ index (faiss::IndexPQ::search, IndexPQ.cpp:124-358; scan_pq.hip): the exhaustive scan of `codes` [ntotal][M] for nq
+// queries over their tables qtab [nq][M][ksub] (distance tables, inner-product tables or rows gathered from the SDC table).
+// Grid, tile, slices, summation order, filter and LDS are plan_pq_scan's decision (pq_plan.h); the caller copies its S and
+// slice_len here.  part: [nq][S][k] keys of scratch when S > 1.  qcodes [nq][M] / ht / n_pass: the polysemous filter
+// (n_pass += codes that passed).  neg: 0, or 0x80000000 under inner product (rows descending, padded -FLT_MAX).  false: not built.
+struct PqScanArgs {
+    const uint8_t* codes;
+    const float* qtab;
+    const uint8_t* qcodes;
+    float* D;
+    int64_t* I;
+    unsigned long long* part;
+    unsigned long long* n_pass;
+    int64_t nq, ntotal, slice_len;
+    int M, ksub, k, S, ht;
+    uint32_t neg;
+};
+bool launch_scan_pq(const PqScanArgs& a, const PqPlan& P, hipStream_t s);
+// compute_code_from_distance_table of n tables [n][M][ksub] (ProductQuantizer.cpp:363-383): codes [n][M]
+void launch_pq_table_argmin(const float* tabs, int64_t n, int M, int ksub, uint8_t* codes, hipStream_t s);
+// compute_sdc_table (ProductQuantizer.cpp:595-616): sdc [M][ksub][ksub]; and the per-query tables search_sdc reads (:644-648)
+void launch_pq_sdc_table(const float* cent, int M, int ksub, int dsub, float* sdc, hipStream_t s);
+void launch_pq_sdc_gather(const float* sdc, const uint8_t* qcodes, int64_t n, int M, int ksub, float* tabs, hipStream_t s);
+void launch_iota(int64_t* out, int64_t n, int64_t base, hipStream_t s);       // out[i] = base + i
 
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this

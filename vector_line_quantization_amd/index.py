@@ -628,6 +628,145 @@ class GpuIVFSQ(_GpuIVF):
         return super().last_scan_info()
 
 
+class GpuPQ:
+    """faiss::IndexPQ (IndexPQ.h:28-117; "PQx" of index_factory): every stored code is scored for every query.  metric "l2":
+    ascending distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are scan
+    positions.  search_type: "pq" (ADC), "sdc", "polysemous", "polysemous_generalize", or Search_type_t's number
+    (include/vlq_ivfpq.h, vlq_pq_*)."""
+
+    METRICS = GpuIVFPQ.METRICS
+    SEARCH_TYPES = {"pq": 0, "he": 1, "generalized_he": 2, "sdc": 3, "polysemous": 4, "polysemous_generalize": 5}   # IndexPQ::Search_type_t
+    _out = GpuIVFPQ._out
+
+    def __init__(self, d, M, nbits=8, metric="l2", device=0):
+        self.d, self.M, self.nbits, self.device = d, M, nbits, device
+        self.ksub = 1 << nbits
+        self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        self.metric = metric
+        check(lib().vlq_pq_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(M), C.c_int(nbits), C.c_int(self.METRICS[metric])))
+        self._search_type = 0
+        self._polysemous_ht = nbits * M + 1
+
+    def _call(self, name, *args):
+        check(getattr(lib(), "vlq_pq_" + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_pq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # --- state ------------------------------------------------------------
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_centroids(self, c):
+        """ProductQuantizer::centroids [M][ksub][dsub]"""
+        p, _k = _ptr(c, np.float32)
+        self._call("set_centroids", p)
+
+    def set_codes(self, codes):
+        """IndexPQ::codes [ntotal][M] uint8; replaces the stored codes"""
+        p, _k = _ptr(codes, np.uint8)
+        self._call("set_codes", p, C.c_int64(codes.shape[0]))
+
+    def add(self, x):
+        px, _a = _ptr(x, np.float32)
+        self._call("add", C.c_int64(x.shape[0]), px)
+
+    def encode(self, x):
+        """the codes [n][M] add would store; nothing is stored"""
+        px, _a = _ptr(x, np.float32)
+        codes = np.empty((x.shape[0], self.M), np.uint8)
+        self._call("encode", C.c_int64(x.shape[0]), px, codes.ctypes.data_as(C.c_void_p))
+        return codes
+
+    def codes(self, i0=0, ni=None):
+        """stored codes i0 .. i0 + ni - 1 in scan order, [ni][M] uint8"""
+        ni = self.ntotal - i0 if ni is None else ni
+        out = np.empty((ni, self.M), np.uint8)
+        self._call("get_codes", C.c_int64(i0), C.c_int64(ni), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_pq_ntotal(self._h))
+
+    def reset(self):
+        self._call("reset")
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    def _set_search(self, search_type, ht):
+        st = self.SEARCH_TYPES.get(search_type, search_type)
+        if st not in self.SEARCH_TYPES.values():
+            raise ValueError("search type %r (one of %s)" % (search_type, ", ".join(repr(s) for s in self.SEARCH_TYPES)))
+        self._call("set_search_type", C.c_int(int(st)), C.c_int(int(ht)))
+        self._search_type, self._polysemous_ht = int(st), int(ht)
+
+    @property
+    def search_type(self):
+        return self._search_type
+
+    @search_type.setter
+    def search_type(self, search_type):
+        self._set_search(search_type, self._polysemous_ht)
+
+    @property
+    def polysemous_ht(self):
+        return self._polysemous_ht
+
+    @polysemous_ht.setter
+    def polysemous_ht(self, ht):
+        self._set_search(self._search_type, ht)
+
+    # --- search -----------------------------------------------------------
+    def search(self, x, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def query_tables(self, x):
+        """the tables the scan reads for x, [n][M][ksub] float32"""
+        px, _a = _ptr(x, np.float32)
+        out = np.empty((x.shape[0], self.M, self.ksub), np.float32)
+        self._call("query_tables", C.c_int64(x.shape[0]), px, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def query_codes(self, x):
+        """the queries' codes the polysemous filter / SDC reads, [n][M] uint8"""
+        px, _a = _ptr(x, np.float32)
+        out = np.empty((x.shape[0], self.M), np.uint8)
+        self._call("query_codes", C.c_int64(x.shape[0]), px, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def stats(self, reset=False):
+        """IndexPQStats since the last reset: (nq, ncode, n_hamming_pass)"""
+        nq, nc, nh = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._call("stats", C.byref(nq), C.byref(nc), C.byref(nh), C.c_int(int(reset)))
+        return nq.value, nc.value, nh.value
+
+    def set_scan_split(self, query_tile=0, slices=0):
+        """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
+        self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
+
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
