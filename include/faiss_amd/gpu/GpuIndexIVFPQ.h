@@ -9,24 +9,12 @@
 
 #include "compat.h"
 #include "../../vlq_line.h"
+#include "GpuIndexFlat.h"        // MemorySpace, GpuIndexConfig, GpuIndexFlatConfig, GpuIndex
 #include "GpuIndicesOptions.h"
 #include "GpuResources.h"
 
 namespace faiss { namespace gpu {
 
-enum class MemorySpace { Device = 1, Unified = 2 };   // gpu/utils/MemorySpace.h
-
-struct GpuIndexConfig {
-  GpuIndexConfig() : device(0), memorySpace(MemorySpace::Device) {}
-  int device;
-  MemorySpace memorySpace;
-};
-struct GpuIndexFlatConfig : public GpuIndexConfig {
-  GpuIndexFlatConfig() : useFloat16(false), useFloat16Accumulator(false), storeTransposed(false) {}
-  bool useFloat16;              ///< accepted; the coarse quantizer stays fp32 here (superset precision)
-  bool useFloat16Accumulator;
-  bool storeTransposed;         ///< layout hint of the reference's cuBLAS call; no effect here
-};
 struct GpuIndexIVFConfig : public GpuIndexConfig {
   GpuIndexIVFConfig() : indicesOptions(INDICES_64_BIT) {}
   IndicesOptions indicesOptions;
@@ -36,23 +24,6 @@ struct GpuIndexIVFPQConfig : public GpuIndexIVFConfig {
   GpuIndexIVFPQConfig() : useFloat16LookupTables(false), usePrecomputedTables(false) {}
   bool useFloat16LookupTables;  ///< VLQ search (16 x 8 bit): half tables as in the reference; IVFPQ search: fp32 (superset precision)
   bool usePrecomputedTables;
-};
-
-class GpuIndex : public faiss::Index {
- public:
-  GpuIndex(GpuResources* resources, int dims, faiss::MetricType metric, GpuIndexConfig config)
-      : Index(dims, metric), resources_(resources), device_(config.device), memorySpace_(config.memorySpace) {
-    FAISS_THROW_IF_NOT_MSG(resources_, "null GpuResources");
-    FAISS_THROW_IF_NOT_MSG(metric == METRIC_L2 || metric == METRIC_INNER_PRODUCT, "unknown metric");
-    resources_->initializeForDevice(device_);
-  }
-  int getDevice() const { return device_; }
-  GpuResources* getResources() { return resources_; }
-
- protected:
-  GpuResources* resources_;
-  const int device_;
-  const MemorySpace memorySpace_;
 };
 
 class GpuIndexIVFPQ : public GpuIndex {

@@ -562,6 +562,54 @@ int vlq_pq_set_scan_split(vlq_pq_t h, int query_tile, int slices);
  *   "kernel=scan_pq_kernel<4, 1, group4, none, 16> Q=4 S=2 slice=500000 lds=73744 join=1".  Synchronises the stream. */
 int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Flat exact k-NN index: faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (IndexFlat.cpp:30-56, :118-121; gpu::GpuIndexFlat) on the
+ * device.  The vectors are stored as rows of 4 * d bytes with their squared norms beside them; add appends on the device and
+ * computes the norms of the new rows only.  search is IndexFlat::search (IndexFlat.cpp:41-56): knn_L2sqr / knn_inner_product
+ * (utils.cpp:726-946), whose dispatch (:741, :939) is decided by the n of the WHOLE call, never by a page of it:
+ *   L2 (metric 1)
+ *     n < 20 && d % 4 == 0   knn_L2sqr_sse (utils.cpp:757-786): fvec_L2sqr per pair (:481-506), four lane accumulators, sub /
+ *                            mul / add not fused, (s0 + s1) + (s2 + s3)
+ *     otherwise              knn_L2sqr_blas (utils.cpp:834-901): (|x|^2 + |y|^2) - 2 ip (:884) with the norms in fvec_norm_L2sqr's
+ *                            order (:538-556) and ip the fmaf chain over k = 0 .. d-1 from 0, this library's standing definition
+ *                            of the reference's sgemm_ (whose own order is the BLAS vendor's)
+ *     rows ascending, padded FLT_MAX / -1
+ *   inner product (metric 0)
+ *     n < 20 && d % 4 == 0   knn_inner_product_sse (utils.cpp:726-755): fvec_inner_product (:509-533), four lane accumulators,
+ *                            multiply and add not fused, the zero tail added, (s0 + s1) + (s2 + s3)
+ *     otherwise              knn_inner_product_blas (utils.cpp:790-829): the fmaf chain
+ *     rows descending, among equal products the lower position first, padded -FLT_MAX / -1
+ * Selection is by the total order (distance, position) everywhere, so the rows depend on no tiling, slicing, chunking or paging
+ * choice; they equal the reference's heap result up to the order inside groups of exactly equal distance.
+ * No scratch grows with n * ntotal: the GEMM path selects inside the distance kernel for k <= 256 (no distance reaches memory),
+ * and walks the database in column chunks behind a bounded matrix for larger k and on the small-batch path.
+ * Limits: k in 1 .. VLQ_MAX_K (k > ntotal pads, ntotal == 0 gives padded rows), ntotal < 2^32 (the key's position field), any
+ * d >= 1 on the GEMM path; the small-batch path holds one query in LDS (d up to about 30 000: VLQ_ERR_UNSUPPORTED beyond).
+ * Not built: range_search, compute_distance_subset, remove_ids, float16 storage.  Pointers [h|d]. */
+typedef struct vlq_flat_s* vlq_flat_t;
+
+/* metric: 0 = inner product, 1 = L2 (MetricType of Index.h); any other value: VLQ_ERR_INVALID */
+int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric);
+void vlq_flat_destroy(vlq_flat_t h);
+int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream);
+/* IndexFlat::add (IndexFlat.cpp:24-28): x[n*d] [h|d] appended in input order; label of a vector = its position */
+int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x);
+int64_t vlq_flat_ntotal(vlq_flat_t h);
+/* IndexFlat::reset (IndexFlat.cpp:35-38) */
+int vlq_flat_reset(vlq_flat_t h);
+int vlq_flat_reserve_memory(vlq_flat_t h, int64_t num_vecs);
+/* IndexFlat::reconstruct / xb (IndexFlat.cpp:118-121): the stored bits of vectors i0 .. i0+n-1, out[n*d] [h|d] */
+int vlq_flat_reconstruct_n(vlq_flat_t h, int64_t i0, int64_t n, float* out);
+/* IndexFlat::search: x[n*d], D[n*k], I[n*k] [h|d] */
+int vlq_flat_search(vlq_flat_t h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* Speed only, results never depend on it: query rows per workgroup of the fused GEMM scan (0, 32, 64, 128; a tile that does
+ * not fit LDS at the call's k shrinks) and column slices (0 .. 64; never cut below one 128-column tile); 0 = the plan decides */
+int vlq_flat_set_scan_split(vlq_flat_t h, int row_tile, int slices);
+/* Introspection, speed only: the last search's plan as text,
+ *   "path=gemm route=fused kernel=knn_gemm_kernel rows=128 S=4 slice=250000 chunk=0 page=32768 lds=141824 join=1".
+ * Synchronises the stream. */
+int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,9 @@ SYMBOLS = [
     "vlq_pq_create", "vlq_pq_destroy", "vlq_pq_set_stream", "vlq_pq_set_centroids", "vlq_pq_set_codes", "vlq_pq_add", "vlq_pq_encode",
     "vlq_pq_get_codes", "vlq_pq_ntotal", "vlq_pq_reset", "vlq_pq_reserve_memory", "vlq_pq_set_search_type", "vlq_pq_search",
     "vlq_pq_query_tables", "vlq_pq_query_codes", "vlq_pq_stats", "vlq_pq_set_scan_split", "vlq_pq_last_scan_info",
+    # flat exact k-NN (vlq_flat_t)
+    "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
+    "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -108,6 +111,8 @@ def lib():
         L.vlq_ivfsq_destroy.restype = None
         L.vlq_pq_ntotal.restype = C.c_int64
         L.vlq_pq_destroy.restype = None
+        L.vlq_flat_ntotal.restype = C.c_int64
+        L.vlq_flat_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "knn_plan.h"
 #include "pq_plan.h"
 #include "scan_plan.h"
 
@@ -361,6 +362,28 @@ void launch_pq_table_argmin(const float* tabs, int64_t n, int M, int ksub, uint8
 void launch_pq_sdc_table(const float* cent, int M, int ksub, int dsub, float* sdc, hipStream_t s);
 void launch_pq_sdc_gather(const float* sdc, const uint8_t* qcodes, int64_t n, int M, int ksub, float* tabs, hipStream_t s);
 void launch_iota(int64_t* out, int64_t n, int64_t base, hipStream_t s);       // out[i] = base + i
+
+// Flat exact k-NN (faiss::IndexFlat::search, IndexFlat.cpp:30-56, utils.cpp:726-946; scan_knn.hip): one page (nq <= P.page) of
+// queries xq [nq][d] against the stored vectors xb [ntotal][d].  Path, route, row tile, slices, chunk and LDS are plan_knn's
+// decision (knn_plan.h) for the WHOLE call.  yn: |y|^2 of the stored vectors, qn: |x|^2 of the page's queries (fvec_norm_L2sqr's
+// order; L2 on the GEMM path only).  part: the partial rows' keys (fused: [nq][S][k] when S > 1; matrix: [nq][S + 1][k]);
+// matrix: [nq][chunk] floats (matrix route); zeros: max(nq, chunk) zero floats (inner product on the GEMM matrix route).
+// ip: rows descending, padded -FLT_MAX / -1.  false: not built.
+struct KnnArgs {
+    const float* xb;
+    const float* yn;
+    const float* xq;
+    const float* qn;
+    float* D;
+    int64_t* I;
+    unsigned long long* part;
+    float* matrix;
+    const float* zeros;
+    int64_t nq, ntotal;
+    int d, k;
+    bool ip;
+};
+bool launch_knn(const KnnArgs& a, const KnnPlan& P, hipStream_t s);
 
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this

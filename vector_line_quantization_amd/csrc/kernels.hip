@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <utility>
+#include "mfma_tile.cuh"
 #include "sse_order.cuh"
 #include "wave_topk.cuh"
 #include "scan_common.cuh"
@@ -76,19 +77,17 @@ void launch_row_norms(const float* x, int64_t n, int d, float* out, hipStream_t 
 // natural order -- bit-identical to a scalar fmaf chain.
 // Row stride KC/2+4 floats keeps the b128 reads bank-conflict free.
 // ---------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
+// (the staging and the MFMA loop are mfma_tile.cuh's, shared with the flat k-NN scan of scan_knn.hip)
 template <int KC>
 __global__ __launch_bounds__(256) void coarse_dist_kernel(
     const float* __restrict__ Q, const float* __restrict__ Cn, const float* __restrict__ qn,
     const float* __restrict__ cn, float* __restrict__ out, int64_t nq, int nlist, int d) {
-    constexpr int S = KC / 2 + 4;
+    typedef MfmaTile<KC, 2, 2, 2> Tile;
     extern __shared__ __attribute__((aligned(16))) float sm[];   // [2 mat][2 parity][128][S]
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int64_t i0 = (int64_t)blockIdx.y * 128;
     const int j0 = blockIdx.x * 128;
-    const bool vec_ok = (d % 4 == 0);
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -98,59 +97,7 @@ __global__ __launch_bounds__(256) void coarse_dist_kernel(
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 
-    for (int k0 = 0; k0 < d; k0 += KC) {
-        for (int f = t; f < 128 * (KC / 4); f += 256) {
-            const int row = f / (KC / 4), v = f % (KC / 4);
-            const int kk = k0 + 4 * v;
-#pragma unroll
-            for (int mat = 0; mat < 2; mat++) {
-                const float* base = mat == 0 ? Q : Cn;
-                const int64_t grow = mat == 0 ? i0 + row : (int64_t)j0 + row;
-                const int64_t lim = mat == 0 ? nq : (int64_t)nlist;
-                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (grow < lim) {
-                    const float* p = base + grow * d + kk;
-                    if (vec_ok && kk + 4 <= d) {
-                        x = *reinterpret_cast<const float4*>(p);
-                    } else {
-                        if (kk + 0 < d) x.x = p[0];
-                        if (kk + 1 < d) x.y = p[1];
-                        if (kk + 2 < d) x.z = p[2];
-                        if (kk + 3 < d) x.w = p[3];
-                    }
-                }
-                float* even = sm + ((mat * 2 + 0) * 128 + row) * S + 2 * v;
-                float* odd = sm + ((mat * 2 + 1) * 128 + row) * S + 2 * v;
-                *reinterpret_cast<float2*>(even) = make_float2(x.x, x.z);
-                *reinterpret_cast<float2*>(odd) = make_float2(x.y, x.w);
-            }
-        }
-        __syncthreads();
-        const int h = lane >> 5, r = lane & 31;
-#pragma unroll
-        for (int u = 0; u < KC / 8; u++) {
-            float4 a[2], b[2];
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++) {
-                a[ti] = *reinterpret_cast<const float4*>(
-                    sm + ((0 * 2 + h) * 128 + wr * 64 + ti * 32 + r) * S + 4 * u);
-                b[ti] = *reinterpret_cast<const float4*>(
-                    sm + ((1 * 2 + h) * 128 + wc * 64 + ti * 32 + r) * S + 4 * u);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-#pragma unroll
-                for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                    for (int tj = 0; tj < 2; tj++) {
-                        const float av = e == 0 ? a[ti].x : e == 1 ? a[ti].y : e == 2 ? a[ti].z : a[ti].w;
-                        const float bv = e == 0 ? b[tj].x : e == 1 ? b[tj].y : e == 2 ? b[tj].z : b[tj].w;
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[ti][tj], 0, 0, 0);
-                    }
-            }
-        }
-        __syncthreads();
-    }
+    Tile::accumulate(Q, i0, nq, Cn, j0, nlist, d, sm, acc);
 
     // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
     const int h = lane >> 5, cidx = lane & 31;

@@ -1,0 +1,223 @@
+// C ABI of the flat exact k-NN index (include/vlq_ivfpq.h, vlq_flat_*): faiss::IndexFlat / gpu::GpuIndexFlat on the device.
+// Host-side orchestration only: the vectors live in a one-list ListStore as rows of 4 * d bytes (lists.h: growth, reserve and
+// the device-side append come from there, as IVFFlat stores its lists), their squared norms in a buffer that grows with it
+// (launch_row_norms over the appended rows only), the scan is scan_knn.hip under plan_knn (knn_plan.h).
+#include "handle.h"
+#include "knn_plan.h"
+#include "lists.h"
+
+struct vlq_flat_s {
+    vlq_ivfpq_s st;               // the device, the stream and the staging of inputs / outputs (set_dev, stage_in, StagedRows): nothing else of it is used
+    int d = 0;
+    int metric = 1;               // MetricType (Index.h): 0 = inner product, 1 = L2
+    int force_rows = 0, force_s = 0;      // vlq_flat_set_scan_split
+    int64_t ntotal = 0;
+    vlq::ListStore lists;         // one list: the vectors in input order, ids = positions
+    DevBuf norms;                 // [capacity] |y|^2 in fvec_norm_L2sqr's order
+    DevBuf ws_x, ws_assign, ws_qn, ws_part, ws_matrix, ws_zero, ws_D, ws_I;
+    size_t zero_floats = 0;       // floats of ws_zero known to be zero
+    char last_scan[224] = "";
+};
+
+namespace {
+
+// room for n norms, the stored ones kept
+int norms_reserve(vlq_flat_t h, int64_t n) {
+    if ((size_t)n * 4 <= h->norms.cap) return VLQ_OK;
+    DevBuf grown;
+    TRY(grown.reserve((size_t)(n + n / 4) * 4));
+    if (h->ntotal > 0) HIP_TRY(hipMemcpyAsync(grown.p, h->norms.p, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->st.stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));       // the old block is freed below
+    h->norms = std::move(grown);
+    return VLQ_OK;
+}
+
+int flat_plan_fail(vlq_flat_t h, int64_t n, int k, const vlq::KnnPlan& P) {
+    return fail(VLQ_ERR_UNSUPPORTED, "flat search of n=%lld, ntotal=%lld, d=%d, k=%d is not built: %s", (long long)n, (long long)h->ntotal,
+                h->d, k, P.why);
+}
+
+// one page of device queries under the call's plan
+int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float* xd, int k, float* Dd, int64_t* Id) {
+    const bool ip = h->metric == 0;
+    vlq::KnnArgs a = {};
+    a.xb = h->lists.codes.as<float>();
+    a.yn = h->norms.as<float>();
+    a.xq = xd;
+    a.D = Dd; a.I = Id;
+    a.nq = n; a.ntotal = h->ntotal; a.d = h->d; a.k = k; a.ip = ip;
+    if (P.path == vlq::kKnnGemm && !ip) {
+        TRY(h->ws_qn.reserve((size_t)n * 4));
+        vlq::launch_row_norms(xd, n, h->d, h->ws_qn.as<float>(), h->st.stream);
+        a.qn = h->ws_qn.as<float>();
+    }
+    if (P.route == vlq::kKnnFused) {
+        if (P.join) TRY(h->ws_part.reserve((size_t)n * P.S * k * 8));
+    } else {
+        TRY(h->ws_part.reserve((size_t)n * (P.S + 1) * k * 8));
+        TRY(h->ws_matrix.reserve((size_t)n * (size_t)P.chunk * 4 + 16));
+        if (ip && P.path == vlq::kKnnGemm) {
+            const size_t nz = (size_t)std::max<int64_t>(n, P.chunk);
+            if (nz > h->zero_floats) {
+                TRY(h->ws_zero.reserve(nz * 4));
+                HIP_TRY(hipMemsetAsync(h->ws_zero.p, 0, nz * 4, h->st.stream));
+                h->zero_floats = nz;
+            }
+            a.zeros = h->ws_zero.as<float>();
+        }
+    }
+    a.part = h->ws_part.as<unsigned long long>();
+    a.matrix = h->ws_matrix.as<float>();
+    if (!vlq::launch_knn(a, P, h->st.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat search: no kernel for rows=%d kpl=%d (%s / %s)", P.rows, P.kpl,
+                                                        vlq::knn_path_name(P.path), vlq::knn_route_name(P.route));
+    HIP_TRY(hipGetLastError());
+    return VLQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric) {
+    if (!out) return fail(VLQ_ERR_INVALID, "null out");
+    *out = nullptr;
+    if (d <= 0) return fail(VLQ_ERR_INVALID, "d=%d must be positive", d);
+    if (d > (1 << 26)) return fail(VLQ_ERR_UNSUPPORTED, "d=%d: rows beyond 2^28 bytes", d);
+    if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
+    const int ndev = vlq_device_count();
+    if (ndev <= 0) return fail(VLQ_ERR_HIP, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(VLQ_ERR_INVALID, "device %d out of range", device);
+    vlq_flat_s* h = new (std::nothrow) vlq_flat_s();
+    if (!h) return fail(VLQ_ERR_INVALID, "out of memory");
+    h->st.device = device;
+    h->d = d; h->metric = metric;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st.own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { delete h; return fail(VLQ_ERR_HIP, "device init failed: %s", hipGetErrorString(e)); }
+    h->st.stream = h->st.own_stream;
+    int rc = h->ws_part.reserve(16);
+    if (rc == VLQ_OK) rc = h->ws_matrix.reserve(16);
+    if (rc == VLQ_OK) rc = h->norms.reserve(16);
+    if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, 1, 4 * d, 0, h->st.stream);
+    if (rc != VLQ_OK) { vlq_flat_destroy(h); return rc; }
+    *out = h;
+    return VLQ_OK;
+}
+
+void vlq_flat_destroy(vlq_flat_t h) {
+    if (!h) return;
+    (void)hipSetDevice(h->st.device);
+    (void)hipStreamSynchronize(h->st.stream);
+    const hipStream_t own = h->st.own_stream;
+    delete h;       // every DevBuf frees its block here, before the stream goes
+    if (own) (void)hipStreamDestroy(own);
+}
+
+int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    TRY(set_dev(&h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    h->st.stream = reinterpret_cast<hipStream_t>(hip_stream);
+    return VLQ_OK;
+}
+
+// IndexFlat::add (IndexFlat.cpp:24-28): appended in input order; only the new rows' norms are computed
+int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (n < 0 || (n > 0 && !x)) return fail(VLQ_ERR_INVALID, "bad argument: n=%lld", (long long)n);
+    if (n == 0) return VLQ_OK;
+    if (h->ntotal + n >= (int64_t(1) << 32))
+        return fail(VLQ_ERR_UNSUPPORTED, "ntotal=%lld beyond 2^32 - 1, the key's position field", (long long)(h->ntotal + n));
+    TRY(set_dev(&h->st));
+    const void* xd;
+    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(h->ws_assign.reserve((size_t)n * 8));
+    HIP_TRY(hipMemsetAsync(h->ws_assign.p, 0, (size_t)n * 8, h->st.stream));       // every vector goes to list 0
+    TRY(norms_reserve(h, h->ntotal + n));
+    int64_t placed = 0;
+    TRY(vlq::lists_append(h->lists, n, h->ws_assign.as<int64_t>(), nullptr, (const uint8_t*)xd, nullptr, nullptr, h->ntotal, h->st.stream,
+                          &placed));
+    // (the one list starts at 0: the new rows sit behind the stored ones)
+    vlq::launch_row_norms(h->lists.codes.as<float>() + (size_t)h->ntotal * h->d, placed, h->d, h->norms.as<float>() + h->ntotal, h->st.stream);
+    HIP_TRY(hipGetLastError());
+    h->ntotal += placed;
+    return VLQ_OK;
+}
+
+int64_t vlq_flat_ntotal(vlq_flat_t h) { return h ? h->ntotal : -1; }
+
+// IndexFlat::reset (IndexFlat.cpp:35-38)
+int vlq_flat_reset(vlq_flat_t h) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    TRY(set_dev(&h->st));
+    TRY(vlq::lists_clear(h->lists, h->st.stream));
+    h->ntotal = 0;
+    return VLQ_OK;
+}
+
+int vlq_flat_reserve_memory(vlq_flat_t h, int64_t num_vecs) {
+    if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument: num_vecs=%lld", (long long)num_vecs);
+    if (num_vecs >= (int64_t(1) << 32)) return fail(VLQ_ERR_UNSUPPORTED, "num_vecs=%lld beyond 2^32 - 1, the key's position field", (long long)num_vecs);
+    TRY(set_dev(&h->st));
+    TRY(norms_reserve(h, num_vecs));
+    return vlq::lists_reserve(h->lists, num_vecs, h->st.stream);
+}
+
+int vlq_flat_reconstruct_n(vlq_flat_t h, int64_t i0, int64_t n, float* out) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (n < 0 || (n > 0 && (i0 < 0 || i0 + n > h->ntotal)))
+        return fail(VLQ_ERR_INVALID, "vectors %lld .. %lld outside 0 .. ntotal=%lld", (long long)i0, (long long)(i0 + n), (long long)h->ntotal);
+    if (n == 0) return VLQ_OK;
+    if (!out) return fail(VLQ_ERR_INVALID, "null out");
+    TRY(set_dev(&h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    HIP_TRY(hipMemcpy(out, h->lists.codes.as<float>() + (size_t)i0 * h->d, (size_t)n * h->d * 4, hipMemcpyDefault));      // (the one list starts at 0)
+    return VLQ_OK;
+}
+
+// IndexFlat::search (IndexFlat.cpp:41-56)
+int vlq_flat_search(vlq_flat_t h, int64_t n, const float* x, int k, float* D, int64_t* I) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
+    if (n > 0 && (!x || !D || !I)) return fail(VLQ_ERR_INVALID, "null buffer");
+    if (k < 1) return fail(VLQ_ERR_INVALID, "k=%d must be positive", k);
+    if (k > VLQ_MAX_K) return fail(VLQ_ERR_UNSUPPORTED, "k=%d beyond %d", k, VLQ_MAX_K);
+    if (n == 0) return VLQ_OK;
+    // the dispatch and the plan are the call's: a last short page takes the path of the first (utils.cpp:741, :939)
+    const vlq::KnnPlan P = vlq::plan_knn(n, h->ntotal, h->d, k, h->force_rows, h->force_s);
+    if (!P.ok) return flat_plan_fail(h, n, k, P);
+    TRY(set_dev(&h->st));
+    StagedRows out;
+    TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I, true));
+    const void* xd = nullptr;
+    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    for (int64_t i0 = 0; i0 < n; i0 += P.page) {
+        const int64_t ni = std::min(P.page, n - i0);
+        TRY(flat_search_page(h, P, ni, (const float*)xd + i0 * h->d, k, (float*)out.D + i0 * k, (int64_t*)out.I + i0 * k));
+    }
+    snprintf(h->last_scan, sizeof(h->last_scan), "path=%s route=%s kernel=%s rows=%d S=%d slice=%lld chunk=%lld page=%lld lds=%zu join=%d",
+             vlq::knn_path_name(P.path), vlq::knn_route_name(P.route),
+             P.route == vlq::kKnnFused ? "knn_gemm_kernel" : P.path == vlq::kKnnDirect ? "knn_direct_kernel" : "coarse_dist+knn_select_kernel",
+             P.rows, P.S, (long long)P.slice_len, (long long)P.chunk, (long long)P.page, P.lds, P.join ? 1 : 0);
+    return out.finish(&h->st);
+}
+
+// speed only: results never depend on it
+int vlq_flat_set_scan_split(vlq_flat_t h, int row_tile, int slices) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (row_tile != 0 && row_tile != 32 && row_tile != 64 && row_tile != 128) return fail(VLQ_ERR_INVALID, "row_tile %d (0, 32, 64 or 128)", row_tile);
+    if (slices < 0 || slices > vlq::kKnnMaxSlices) return fail(VLQ_ERR_INVALID, "slices %d outside 0..%d", slices, vlq::kKnnMaxSlices);
+    h->force_rows = row_tile;
+    h->force_s = slices;
+    return VLQ_OK;
+}
+
+int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap) {
+    if (!h || !buf || cap < 1) return fail(VLQ_ERR_INVALID, "null argument");
+    TRY(set_dev(&h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    snprintf(buf, (size_t)cap, "%s", h->last_scan[0] ? h->last_scan : "kernel=none");
+    return VLQ_OK;
+}
+
+}  // extern "C"

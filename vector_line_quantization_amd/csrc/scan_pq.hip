@@ -18,6 +18,7 @@
 // is exact), the rows come out descending, padded -FLT_MAX.
 #include "kernels.h"
 #include "pq_plan.h"
+#include "join_rows.cuh"
 #include "wave_topk.cuh"
 
 #include <type_traits>
@@ -62,24 +63,6 @@ __device__ __forceinline__ int code_hd(uint32_t x) {
     // differing bytes (generalized_hamming_64): OR every byte's bits into its lowest one
     x |= x >> 1; x |= x >> 2; x |= x >> 4;
     return __popc(x & 0x01010101u);
-}
-
-__device__ __forceinline__ float flip_sign(float v, uint32_t neg) { return __uint_as_float(__float_as_uint(v) ^ neg); }
-
-// rows out of a finished selection: (distance, position), padded FLT_MAX / -1 (Heap.h:318-321); neg = 0x80000000 under inner product
-template <int KPL, typename Sel>
-__device__ __forceinline__ void pq_emit(const Sel& sel, int k, uint32_t neg, float* __restrict__ D, int64_t* __restrict__ I, int lane) {
-#pragma unroll
-    for (int r = 0; r < KPL; r++) {
-        const int e = r * 64 + lane;
-        if (e >= k) continue;
-        const u64 key = sel.best[r];
-        float dis = 3.402823466e+38f;
-        int64_t id = -1;
-        if (key != kMaxKey) { dis = ordered_to_f32((uint32_t)(key >> 32)); id = (int64_t)(uint32_t)key; }
-        D[e] = flip_sign(dis, neg);
-        I[e] = id;
-    }
 }
 
 // LOAD: bytes of a code per global load (16: rows of M % 16 == 0 bytes, 4: M % 4 == 0, 1: any M)
@@ -288,28 +271,6 @@ __global__ __launch_bounds__(256) void scan_pq_kernel(PqScanArgs a, PqLayout lay
     }
 }
 
-// the S slices' keys of a query -> its row; one wave per query
-template <int KPL>
-__global__ __launch_bounds__(256) void pq_join_kernel(const u64* __restrict__ part, int64_t nq, int S, int k, uint32_t neg,
-                                                      float* __restrict__ D, int64_t* __restrict__ I) {
-    __shared__ u64 queue[4][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t q = (int64_t)blockIdx.x * 4 + wave;
-    if (q >= nq) return;
-    WaveSelect<KPL> sel;
-    sel.init(k, queue[wave], lane);
-    const u64* rows = part + (size_t)q * S * k;
-    for (int s = 0; s < S; s++)
-        for (int e0 = 0; e0 < k; e0 += 64) {
-            const int e = e0 + lane;
-            const bool valid = e < k;
-            sel.offer_key(valid ? rows[(size_t)s * k + e] : kMaxKey, valid);
-        }
-    sel.flush();
-    pq_emit<KPL>(sel, k, neg, D + q * k, I + q * k, lane);
-}
-
 // compute_code_from_distance_table (ProductQuantizer.cpp:363-383): the first j with tab[m][j] below everything before it, from
 // 1e20; no such j leaves idxm = -1, stored as 255.  One wave per (vector, m).
 __global__ __launch_bounds__(256) void pq_table_argmin_kernel(const float* __restrict__ tabs, int64_t n, int M, int ksub, uint8_t* __restrict__ codes) {
@@ -392,12 +353,7 @@ bool launch_scan_pq(const PqScanArgs& a, const PqPlan& P, hipStream_t s) {
     else if (P.kpl == 4) ok = P.Q == 1 ? launch_pq_mode<1, 4>(a, P, tiles, s) : P.Q == 2 ? launch_pq_mode<2, 4>(a, P, tiles, s) : launch_pq_mode<4, 4>(a, P, tiles, s);
     else ok = P.Q == 1 ? launch_pq_mode<1, 1>(a, P, tiles, s) : P.Q == 2 ? launch_pq_mode<2, 1>(a, P, tiles, s) : launch_pq_mode<4, 1>(a, P, tiles, s);
     if (!ok) return false;
-    if (P.join) {
-        const dim3 grid((unsigned)((a.nq + 3) / 4));
-        if (P.kpl == 1) hipLaunchKernelGGL(pq_join_kernel<1>, grid, dim3(256), 0, s, a.part, a.nq, a.S, a.k, a.neg, a.D, a.I);
-        else if (P.kpl == 4) hipLaunchKernelGGL(pq_join_kernel<4>, grid, dim3(256), 0, s, a.part, a.nq, a.S, a.k, a.neg, a.D, a.I);
-        else hipLaunchKernelGGL(pq_join_kernel<16>, grid, dim3(256), 0, s, a.part, a.nq, a.S, a.k, a.neg, a.D, a.I);
-    }
+    if (P.join) launch_join_rows(P.kpl, a.part, a.nq, a.S, (int64_t)a.S * a.k, a.k, a.neg, a.D, a.I, nullptr, 0, s);      // join_rows.cuh
     return true;
 }
 

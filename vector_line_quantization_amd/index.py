@@ -767,6 +767,80 @@ class GpuPQ:
         return buf.value.decode()
 
 
+class GpuFlat:
+    """faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (gpu::GpuIndexFlat): the exact brute-force index.  metric "l2": ascending
+    squared distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are positions in
+    the order of add.  Fewer than 20 queries with d % 4 == 0 take the reference's per-pair SSE order, everything else the fmaf
+    chain of the GEMM path; the call's n decides, never a page's (include/vlq_ivfpq.h, vlq_flat_*)."""
+
+    METRICS = GpuIVFPQ.METRICS
+    _out = GpuIVFPQ._out
+
+    def __init__(self, d, metric="l2", device=0):
+        self.d, self.device = d, device
+        self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        self.metric = metric
+        check(lib().vlq_flat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.METRICS[metric])))
+
+    def _call(self, name, *args):
+        check(getattr(lib(), "vlq_flat_" + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_flat_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def add(self, x):
+        px, _a = _ptr(x, np.float32)
+        self._call("add", C.c_int64(x.shape[0]), px)
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_flat_ntotal(self._h))
+
+    def reset(self):
+        self._call("reset")
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    def reconstruct_n(self, i0=0, n=None, out=None):
+        """the stored bits of vectors i0 .. i0 + n - 1, [n][d] float32 (out: a numpy array or a torch tensor to fill)"""
+        n = self.ntotal - i0 if n is None else n
+        if out is None:
+            out = np.empty((n, self.d), np.float32)
+        self._call("reconstruct_n", C.c_int64(i0), C.c_int64(n), _out_ptr(out, np.float32)[0])
+        return out
+
+    def search(self, x, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def scan_split(self, row_tile=0, slices=0):
+        """speed only: query rows per workgroup of the fused scan (0, 32, 64, 128) and column slices (0 .. 64); 0 = the plan decides"""
+        self._call("set_scan_split", C.c_int(row_tile), C.c_int(slices))
+
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
