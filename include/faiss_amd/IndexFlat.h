@@ -68,4 +68,88 @@ struct IndexFlatIP : IndexFlat {
   IndexFlatIP() {}
 };
 
+/// faiss::IndexRefineFlat (IndexFlat.h:103-140, IndexFlat.cpp:149-269): queries base_index for k * k_factor candidates and
+/// re-scores them exactly against the uncompressed vectors kept beside it.  refine_index stays an IndexFlat with its host xb
+/// (index_io and callers read it); the re-ranking runs on the device behind vlq_flat_refine (include/vlq_ivfpq.h), against a
+/// private vlq_flat_t that mirrors refine_index's rows: it appends the rows added since the last search and starts over after
+/// reset() or when refine_index holds fewer rows than it has seen (a freshly read index has seen none).  A caller that rewrites
+/// refine_index.xb in place must call reset() and add again.
+struct IndexRefineFlat : Index {
+  IndexFlat refine_index;   ///< storage for full vectors
+  Index* base_index;        ///< faster index to pre-select the vectors that should be filtered
+  bool own_fields;          ///< should the base index be deallocated?
+  float k_factor;           ///< factor between k requested in search and the k requested from the base_index (>= 1)
+  int device = 0;           ///< device of the re-ranking (set before the first search)
+
+  explicit IndexRefineFlat(Index* base_index)
+      : Index(base_index->d, base_index->metric_type), refine_index(base_index->d, base_index->metric_type),
+        base_index(base_index), own_fields(false), k_factor(1) {
+    is_trained = base_index->is_trained;
+    FAISS_THROW_IF_NOT_MSG(base_index->ntotal == 0, "base_index should be empty in the beginning");
+  }
+  IndexRefineFlat() : base_index(nullptr), own_fields(false), k_factor(1) {}
+  ~IndexRefineFlat() override {
+    if (store_) vlq_flat_destroy(store_);
+    if (own_fields) delete base_index;
+  }
+  IndexRefineFlat(const IndexRefineFlat&) = delete;
+  IndexRefineFlat& operator=(const IndexRefineFlat&) = delete;
+
+  void train(idx_t n, const float* x) override {
+    base_index->train(n, x);
+    is_trained = true;
+  }
+  void add(idx_t n, const float* x) override {
+    FAISS_THROW_IF_NOT(is_trained);
+    base_index->add(n, x);
+    refine_index.add(n, x);
+    ntotal = refine_index.ntotal;
+  }
+  void reset() override {
+    base_index->reset();
+    refine_index.reset();
+    ntotal = 0;
+    mirrored_ = -1;
+  }
+
+  void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override {
+    FAISS_THROW_IF_NOT(is_trained);
+    const idx_t k_base = idx_t(k * k_factor);       // IndexFlat.cpp:224
+    FAISS_THROW_IF_NOT_MSG(k >= 1 && k_base >= k && k_base <= VLQ_MAX_K, "k_base = k * k_factor outside k..1024");
+    if (n == 0) return;
+    idx_t* base_labels = labels;
+    float* base_distances = distances;
+    std::vector<idx_t> lab_buf;
+    std::vector<float> dis_buf;
+    if (k != k_base) {      // otherwise the base search runs into the caller's buffers (:225-236)
+      lab_buf.resize((size_t)n * k_base);
+      dis_buf.resize((size_t)n * k_base);
+      base_labels = lab_buf.data();
+      base_distances = dis_buf.data();
+    }
+    base_index->search(n, x, k_base, base_distances, base_labels);
+    sync_store_();
+    // :245-260; a label outside -1 .. ntotal - 1 is the reference's assert (:240-242): VLQ_ERR_INVALID here
+    VLQ_CHECK(vlq_flat_refine(store_, n, x, (int)k_base, base_distances, (const int64_t*)base_labels, (int)k, distances, (int64_t*)labels));
+  }
+
+ private:
+  void sync_store_() const {
+    if (!store_) {
+      VLQ_CHECK(vlq_flat_create(&store_, device, refine_index.d, (int)refine_index.metric_type));
+      mirrored_ = 0;
+    }
+    if (mirrored_ < 0 || refine_index.ntotal < mirrored_) {
+      VLQ_CHECK(vlq_flat_reset(store_));
+      mirrored_ = 0;
+    }
+    if (refine_index.ntotal > mirrored_) {
+      VLQ_CHECK(vlq_flat_add(store_, refine_index.ntotal - mirrored_, refine_index.xb.data() + (size_t)mirrored_ * refine_index.d));
+      mirrored_ = refine_index.ntotal;
+    }
+  }
+  mutable vlq_flat_t store_ = nullptr;
+  mutable idx_t mirrored_ = 0;      // rows of refine_index the store holds; -1: start over
+};
+
 }  // namespace faiss

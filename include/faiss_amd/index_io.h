@@ -6,6 +6,7 @@
 //   "IvFl"  IndexIVFFlat (index_io.cpp:276-283, :597-603)
 //   "IvSQ"  IndexIVFScalarQuantizer (index_io.cpp:208-215, :283-292, :439-447, :611-620)
 //   "IxPq"  IndexPQ (index_io.cpp:259-270); read as well: its older records "IxPQ" and "IxPo" (:578-596)
+//   "IxRF"  IndexRefineFlat (index_io.cpp:336-341, :645-654): header, the base index, the refine IndexFlat, k_factor
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
 // and rejected.
@@ -93,6 +94,12 @@ inline void write_index(const Index* idx, FILE* f) {
     w1(f, fourcc(flat->metric_type == METRIC_L2 ? "IxF2" : "IxFI"));     // index_io.cpp:166-171
     write_header(idx, f);
     wvec(f, flat->xb);
+  } else if (const IndexRefineFlat* idxrf = dynamic_cast<const IndexRefineFlat*>(idx)) {
+    w1(f, fourcc("IxRF"));                     // index_io.cpp:336-341
+    write_header(idx, f);
+    write_index(idxrf->base_index, f);
+    write_index(&idxrf->refine_index, f);
+    w1(f, idxrf->k_factor);
   } else if (const MultiIndexQuantizer* miq = dynamic_cast<const MultiIndexQuantizer*>(idx)) {
     w1(f, fourcc("Imiq"));
     write_header(idx, f);
@@ -170,6 +177,20 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     rvec(f, flat->xb);
     FAISS_THROW_IF_NOT(flat->xb.size() == (size_t)flat->ntotal * flat->d);
     return flat.release();
+  }
+  if (h == fourcc("IxRF")) {                   // index_io.cpp:645-654
+    std::unique_ptr<IndexRefineFlat> idxrf(new IndexRefineFlat());
+    read_header(idxrf.get(), f);
+    idxrf->base_index = read_index(f, precompute);
+    idxrf->own_fields = true;
+    std::unique_ptr<Index> second(read_index(f, precompute));
+    IndexFlat* rf = dynamic_cast<IndexFlat*>(second.get());
+    FAISS_THROW_IF_NOT_MSG(rf, "the refine index of an IxRF record must be an IndexFlat");
+    IndexFlat& own = idxrf->refine_index;      // (a fresh IndexFlat: its device copy is built at its first search)
+    own.d = rf->d; own.ntotal = rf->ntotal; own.verbose = rf->verbose; own.is_trained = rf->is_trained; own.metric_type = rf->metric_type;
+    own.xb.swap(rf->xb);
+    r1(f, idxrf->k_factor);
+    return idxrf.release();
   }
   if (h == fourcc("Imiq")) {
     std::unique_ptr<MultiIndexQuantizer> miq(new MultiIndexQuantizer(2, 2, 1));

@@ -585,7 +585,7 @@ int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap);
  * and walks the database in column chunks behind a bounded matrix for larger k and on the small-batch path.
  * Limits: k in 1 .. VLQ_MAX_K (k > ntotal pads, ntotal == 0 gives padded rows), ntotal < 2^32 (the key's position field), any
  * d >= 1 on the GEMM path; the small-batch path holds one query in LDS (d up to about 30 000: VLQ_ERR_UNSUPPORTED beyond).
- * Not built: range_search, compute_distance_subset, remove_ids, float16 storage.  Pointers [h|d]. */
+ * Not built: range_search, remove_ids, float16 storage.  Pointers [h|d]. */
 typedef struct vlq_flat_s* vlq_flat_t;
 
 /* metric: 0 = inner product, 1 = L2 (MetricType of Index.h); any other value: VLQ_ERR_INVALID */
@@ -609,6 +609,30 @@ int vlq_flat_set_scan_split(vlq_flat_t h, int row_tile, int slices);
  *   "path=gemm route=fused kernel=knn_gemm_kernel rows=128 S=4 slice=250000 chunk=0 page=32768 lds=141824 join=1".
  * Synchronises the stream. */
 int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap);
+
+/* --- IndexRefineFlat: exact re-ranking of a shortlist (IndexFlat.h:103-140, IndexFlat.cpp:149-269) ---
+ * A label is a position in the flat store; a label < 0 is skipped (the reference's `continue`, utils.cpp:984, :1004).  The
+ * distance of a live entry is fvec_L2sqr / fvec_inner_product in the reference's operation order at every n and d: this path has
+ * no BLAS branch (utils.cpp:974-1012), so every distance is bit-reproducible.
+ * Limits of both calls: 1 <= k <= k_base <= VLQ_MAX_K (anything else: VLQ_ERR_INVALID); ntotal < 2^32; any d >= 1 whose query
+ * row fits LDS beside the row tiles and the keys (d up to about 27 000; VLQ_ERR_UNSUPPORTED beyond); an empty store with all
+ * labels < 0 is legal.  A label >= ntotal is never dereferenced: the call returns VLQ_ERR_INVALID (the reference asserts,
+ * IndexFlat.cpp:240-242) and its outputs are undefined; the next call starts clean.  Both calls synchronise the stream once, to
+ * read that flag.  Queries go to the device in pages of 32 768, as vlq_flat_search's.  Pointers [h|d], on the handle's stream. */
+/* IndexFlat::compute_distance_subset (IndexFlat.cpp:73-93): distances[n*k] in / out -- entry (i, j) becomes the distance of
+ * x[i] to vector labels[i*k + j]; entries whose label is < 0 are left untouched */
+int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, int k, float* distances, const int64_t* labels);
+/* The seam of IndexRefineFlat::search, lines 245-260 and nothing else: compute_distance_subset over the shortlist
+ * base_D / base_I [n*k_base], then reorder_2_heaps (IndexFlat.cpp:194-213) into D / I [n*k].  L2: the k smallest by the total
+ * order (distance, shortlist position), ascending; inner product: the k largest, the lower shortlist position first among equals,
+ * descending.  A skipped entry takes part with the distance it carries and its label, so the base's FLT_MAX / -FLT_MAX padding
+ * lands at the end.  Rows equal the reference's heap result up to the order inside groups of exactly equal distance.  D / I may
+ * be base_D / base_I when k == k_base (the reference works in place there); otherwise they must not overlap them. */
+int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const float* base_D, const int64_t* base_I, int k, float* D,
+                    int64_t* I);
+/* Introspection: the kernel shape the last of the two calls ran, as text,
+ *   "kernel=refine_flat_kernel select=1 metric=l2 read=tile128 waves=2 trips=2 slots=128 page=32768 lds=21248" */
+int vlq_flat_last_refine_info(vlq_flat_t h, char* buf, int cap);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,7 @@ SYMBOLS = [
     # flat exact k-NN (vlq_flat_t)
     "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
     "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
+    "vlq_flat_compute_distance_subset", "vlq_flat_refine", "vlq_flat_last_refine_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",

@@ -7,6 +7,7 @@
 
 #include "knn_plan.h"
 #include "pq_plan.h"
+#include "refine_flat_plan.h"
 #include "scan_plan.h"
 
 namespace vlq {
@@ -465,5 +466,24 @@ void launch_refine(const RefineArgs& a, hipStream_t s);
 // out[i] = (x[i] - coarse[assign[i]]) - pq.decode(codes[i])  (IndexIVFPQ.cpp:250-256; assign < 0: zeros)
 void launch_residual2(const float* x, int64_t n, int d, const float* coarse, const int64_t* assign, const float* pq,
                       const uint8_t* codes, int M, int ksub, int dsub, float* out, hipStream_t s);
+
+// IndexRefineFlat (refine_flat.hip): IndexFlat::compute_distance_subset and the re-ranking seam of IndexRefineFlat::search
+// (IndexFlat.cpp:73-93, :245-260) under plan_refine_flat.  labels [nq][k_base] are row positions of xb [ntotal][d], < 0 = skip;
+// a label >= ntotal is never dereferenced: it sets *bad = 1 and counts as skipped.  select: the k best of a row by (distance,
+// shortlist position) go to D / I [nq][k], a skipped entry taking part with its base_D (D / I may be base_D / labels when
+// k == k_base).  !select: D is the [nq][k_base] distances in place, the skipped entries untouched.  false: not built.
+struct RefineFlatArgs {
+    const float* xb;
+    const float* x;              // [nq][d]
+    const int64_t* labels;       // [nq][k_base]
+    const float* base_D;         // [nq][k_base] (select)
+    float* D;
+    int64_t* I;
+    int* bad;
+    int64_t nq, ntotal;
+    int d, k_base, k;
+    bool ip;
+};
+bool launch_refine_flat(const RefineFlatArgs& a, const RefineFlatPlan& P, bool select, hipStream_t s);
 
 }  // namespace vlq

@@ -17,6 +17,9 @@ struct vlq_flat_s {
     DevBuf ws_x, ws_assign, ws_qn, ws_part, ws_matrix, ws_zero, ws_D, ws_I;
     size_t zero_floats = 0;       // floats of ws_zero known to be zero
     char last_scan[224] = "";
+    // vlq_flat_compute_distance_subset / vlq_flat_refine: the staged labels and base distances, the device flag of a label >= ntotal
+    DevBuf ws_rl, ws_rD, refine_bad;
+    char last_refine[160] = "";
 };
 
 namespace {
@@ -72,6 +75,42 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
                                                         vlq::knn_path_name(P.path), vlq::knn_route_name(P.route));
     HIP_TRY(hipGetLastError());
     return VLQ_OK;
+}
+
+// the two entry points of refine_flat.hip: pages of device rows under the call's plan, then the flag of a label >= ntotal.  The
+// flag is read behind every call (one stream synchronisation): the reference asserts there (IndexFlat.cpp:240-242).
+int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int64_t n, const float* xd, const int64_t* ld, int k_base,
+                    const float* bd, int k, float* Dd, int64_t* Id) {
+    TRY(h->refine_bad.reserve(16));
+    HIP_TRY(hipMemsetAsync(h->refine_bad.p, 0, 4, h->st.stream));
+    for (int64_t i0 = 0; i0 < n; i0 += P.page) {
+        vlq::RefineFlatArgs a = {};
+        a.xb = h->lists.codes.as<float>();       // (the one list starts at 0)
+        a.x = xd + i0 * h->d;
+        a.labels = ld + i0 * k_base;
+        a.base_D = bd ? bd + i0 * k_base : nullptr;
+        a.D = Dd + i0 * k;
+        a.I = Id ? Id + i0 * k : nullptr;
+        a.bad = h->refine_bad.as<int>();
+        a.nq = std::min(P.page, n - i0); a.ntotal = h->ntotal; a.d = h->d; a.k_base = k_base; a.k = k; a.ip = h->metric == 0;
+        if (!vlq::launch_refine_flat(a, P, select, h->st.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat refine: no kernel for this plan");
+        HIP_TRY(hipGetLastError());
+    }
+    snprintf(h->last_refine, sizeof(h->last_refine), "kernel=refine_flat_kernel select=%d metric=%s read=%s waves=%d trips=%d slots=%d page=%lld lds=%zu",
+             select ? 1 : 0, h->metric == 0 ? "ip" : "l2", vlq::flat_read_name(P.read), P.waves, P.trips, P.slots, (long long)P.page, P.lds);
+    return VLQ_OK;
+}
+
+int refine_flat_bad(vlq_flat_t h) {
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, h->refine_bad.p, 4, hipMemcpyDeviceToHost, h->st.stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    if (bad) return fail(VLQ_ERR_INVALID, "a label >= ntotal=%lld was passed (IndexFlat.cpp:240-242 asserts); the results of this call are undefined", (long long)h->ntotal);
+    return VLQ_OK;
+}
+
+int refine_flat_plan_fail(vlq_flat_t h, int k_base, int k, const vlq::RefineFlatPlan& P) {
+    return fail(P.err == 2 ? VLQ_ERR_UNSUPPORTED : VLQ_ERR_INVALID, "flat refine of d=%d, k_base=%d, k=%d (at most %d): %s", h->d, k_base, k, VLQ_MAX_K, P.why);
 }
 
 }  // namespace
@@ -217,6 +256,53 @@ int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap) {
     TRY(set_dev(&h->st));
     HIP_TRY(hipStreamSynchronize(h->st.stream));
     snprintf(buf, (size_t)cap, "%s", h->last_scan[0] ? h->last_scan : "kernel=none");
+    return VLQ_OK;
+}
+
+// IndexFlat::compute_distance_subset (IndexFlat.cpp:73-93)
+int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, int k, float* distances, const int64_t* labels) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
+    if (n > 0 && (!x || !distances || !labels)) return fail(VLQ_ERR_INVALID, "null buffer");
+    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k, k, false);
+    if (!P.ok) return refine_flat_plan_fail(h, k, k, P);
+    if (n == 0) return VLQ_OK;
+    TRY(set_dev(&h->st));
+    const void *xd, *ld, *dd;
+    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->st, labels, (size_t)n * k * 8, h->ws_rl, &ld));
+    TRY(stage_in(&h->st, distances, (size_t)n * k * 4, h->ws_rD, &dd));       // in / out: device rows are updated in place
+    TRY(refine_flat_dev(h, P, false, n, (const float*)xd, (const int64_t*)ld, k, nullptr, k, (float*)const_cast<void*>(dd), nullptr));
+    if (dd != (const void*)distances) HIP_TRY(hipMemcpyAsync(distances, dd, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->st.stream));
+    return refine_flat_bad(h);
+}
+
+// the seam of IndexRefineFlat::search (IndexFlat.cpp:245-260): compute_distance_subset on the shortlist, then reorder_2_heaps
+int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const float* base_D, const int64_t* base_I, int k, float* D,
+                    int64_t* I) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
+    if (n > 0 && (!x || !base_D || !base_I || !D || !I)) return fail(VLQ_ERR_INVALID, "null buffer");
+    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k_base, k, true);
+    if (!P.ok) return refine_flat_plan_fail(h, k_base, k, P);
+    if (k != k_base && ((const void*)D == (const void*)base_D || (const void*)I == (const void*)base_I))
+        return fail(VLQ_ERR_INVALID, "D / I may be base_D / base_I only when k == k_base");
+    if (n == 0) return VLQ_OK;
+    TRY(set_dev(&h->st));
+    const void *xd, *ld, *bd;
+    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->st, base_I, (size_t)n * k_base * 8, h->ws_rl, &ld));
+    TRY(stage_in(&h->st, base_D, (size_t)n * k_base * 4, h->ws_rD, &bd));
+    StagedRows out;
+    TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I));
+    TRY(refine_flat_dev(h, P, true, n, (const float*)xd, (const int64_t*)ld, k_base, (const float*)bd, k, (float*)out.D, (int64_t*)out.I));
+    TRY(out.finish(&h->st));
+    return refine_flat_bad(h);
+}
+
+int vlq_flat_last_refine_info(vlq_flat_t h, char* buf, int cap) {
+    if (!h || !buf || cap < 1) return fail(VLQ_ERR_INVALID, "null argument");
+    snprintf(buf, (size_t)cap, "%s", h->last_refine[0] ? h->last_refine : "kernel=none");
     return VLQ_OK;
 }
 

@@ -840,6 +840,159 @@ class GpuFlat:
         self._call("last_scan_info", buf, C.c_int(256))
         return buf.value.decode()
 
+    # --- IndexRefineFlat's seam (IndexFlat.cpp:73-93, :245-260) -----------------
+    def compute_distance_subset(self, x, labels, distances):
+        """IndexFlat::compute_distance_subset: distances [n][k] (written in place, returned) becomes the distance of x[i] to
+        the vector at position labels[i][j]; entries whose label is < 0 are left untouched"""
+        n, k = labels.shape
+        px, _a = _ptr(x, np.float32)
+        pl, _b = _ptr(labels, np.int64)
+        self._call("compute_distance_subset", C.c_int64(n), px, C.c_int(k), _out_ptr(distances, np.float32)[0], pl)
+        return distances
+
+    def refine(self, x, base_D, base_I, k, D=None, I=None):
+        """lines 245-260 of IndexRefineFlat::search: the shortlist base_D / base_I [n][k_base] (labels = positions, < 0 = skip)
+        re-scored exactly and the best k kept.  D / I may be base_D / base_I when k == k_base."""
+        n, k_base = base_I.shape
+        px, _a = _ptr(x, np.float32)
+        pd, _b = _ptr(base_D, np.float32)
+        pl, _c = _ptr(base_I, np.int64)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("refine", C.c_int64(n), px, C.c_int(k_base), pd, pl, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def last_refine_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_refine_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
+VLQ_MAX_K = 1024      # include/vlq_ivfpq.h
+
+
+class GpuRefineFlat:
+    """faiss::IndexRefineFlat (IndexFlat.h:103-140): a base index whose shortlist of k * k_factor candidates is re-scored
+    exactly against the uncompressed vectors kept beside it.  base: GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ or GpuFlat; the
+    refine store is a GpuFlat of the base's d and metric.  A base label must be a position in the store: add() keeps the two in
+    step (IVF bases get the sequential ids ntotal .. ntotal + n - 1); an index whose lists were set with ids 0 .. ntotal - 1
+    gets its store from set_store().  The base and the store share one stream of this object's (set_stream replaces it), so the
+    shortlist of a device-side query never leaves the device."""
+
+    def __init__(self, base):
+        import torch
+        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat)):
+            raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ or GpuFlat, got %s" % type(base).__name__)
+        self.base = base
+        self.d, self.metric, self.device = base.d, base.metric, base.device
+        self.k_factor = 1.0
+        self.nprobe = 1           # IndexIVF's default, used where search() is given none
+        self.store = GpuFlat(self.d, metric=self.metric, device=self.device)
+        self._ivf = isinstance(base, (GpuIVFPQ, _GpuIVF))
+        self._dev = torch.device("cuda", self.device)
+        self._stream = torch.cuda.Stream(device=self._dev)
+        self.set_stream(self._stream.cuda_stream)
+        self._short = None        # (D, I) device tensors of the last shortlist, reused while the shape holds
+
+    def set_stream(self, stream_ptr):
+        self.base.set_stream(stream_ptr)
+        self.store.set_stream(stream_ptr)
+
+    @property
+    def ntotal(self):
+        return self.store.ntotal
+
+    def add(self, x, xids=None):
+        n, n0 = x.shape[0], self.store.ntotal
+        if self.base.ntotal != n0:
+            raise ValueError("the base holds %d vectors and the refine store %d: labels are not store positions (set_store)"
+                             % (self.base.ntotal, n0))
+        ids = np.arange(n0, n0 + n, dtype=np.int64)
+        if xids is not None:
+            given = xids.cpu().numpy() if _is_torch(xids) else np.asarray(xids)
+            if not np.array_equal(given, ids):
+                raise ValueError("GpuRefineFlat.add takes the sequential ids ntotal .. ntotal + n - 1 only: a label is a position "
+                                 "in the refine store")
+        if self._ivf:
+            self.base.add(x, ids)
+        else:
+            self.base.add(x)
+        self.store.add(x)
+
+    def set_store(self, vecs):
+        """the uncompressed vectors [ntotal][d] of a base whose lists were set, not added: vector i is the one with id i"""
+        if vecs.shape[0] != self.base.ntotal:
+            raise ValueError("%d vectors for a base of %d" % (vecs.shape[0], self.base.ntotal))
+        self.store.reset()
+        self.store.add(vecs)
+
+    def reset(self):
+        if hasattr(self.base, "reset"):
+            self.base.reset()
+        else:       # GpuIVFPQ: empty lists
+            self.base.set_lists(np.zeros((0, self.base.M), np.uint8), np.zeros((0,), np.int64), np.zeros((self.base.nlist + 1,), np.int64))
+        self.store.reset()
+
+    def k_base(self, k):
+        """idx_t(k * k_factor), IndexFlat.cpp:224 (one float multiply, truncated)"""
+        if not self.k_factor >= 1:
+            raise ValueError("k_factor=%r must be >= 1" % (self.k_factor,))
+        kb = int(np.float32(k) * np.float32(self.k_factor))
+        if kb < k or kb > VLQ_MAX_K:
+            raise ValueError("k_base = int(k * k_factor) = %d outside k=%d .. %d" % (kb, k, VLQ_MAX_K))
+        return kb
+
+    def _base_search(self, x, k, nprobe, D, I):
+        if self._ivf:
+            return self.base.search(x, self.nprobe if nprobe is None else nprobe, k, D, I)
+        return self.base.search(x, k, D, I)
+
+    def search(self, x, k, nprobe=None, D=None, I=None, store_pairs=False):
+        import torch
+        if store_pairs:
+            raise ValueError("store_pairs labels are (list, offset) pairs, not positions in the refine store")
+        if self.base.ntotal != self.store.ntotal:
+            raise ValueError("the base holds %d vectors and the refine store %d: the base's labels are not store positions "
+                             "(add through GpuRefineFlat, or set_store)" % (self.base.ntotal, self.store.ntotal))
+        if k < 1:
+            raise ValueError("k=%d must be positive" % k)
+        kb = self.k_base(k)
+        n = x.shape[0]
+        host = not (_is_torch(x) and x.is_cuda)
+        xd = torch.as_tensor(np.ascontiguousarray(x, np.float32) if not _is_torch(x) else x).to(self._dev) if host else x
+        if host or D is None:
+            Dd = torch.empty((n, k), dtype=torch.float32, device=self._dev)
+        else:
+            Dd = D
+        if host or I is None:
+            Id = torch.empty((n, k), dtype=torch.int64, device=self._dev)
+        else:
+            Id = I
+        if kb == k:        # the reference's in-place form (IndexFlat.cpp:225-236)
+            bD, bI = Dd, Id
+        else:
+            if self._short is None or self._short[0].shape != (n, kb):
+                self._short = (torch.empty((n, kb), dtype=torch.float32, device=self._dev),
+                               torch.empty((n, kb), dtype=torch.int64, device=self._dev))
+            bD, bI = self._short
+        self._base_search(xd, kb, nprobe, bD, bI)
+        self.store.refine(xd, bD, bI, k, Dd, Id)      # (synchronises the stream: the rows are complete on return)
+        if not host:
+            return Dd, Id
+        Dh, Ih = Dd.cpu().numpy(), Id.cpu().numpy()
+        if D is not None:
+            _out_ptr(D, np.float32)
+            D[...] = Dh
+            Dh = D
+        if I is not None:
+            _out_ptr(I, np.int64)
+            I[...] = Ih
+            Ih = I
+        return Dh, Ih
+
+    def last_refine_info(self):
+        return self.store.last_refine_info()
+
 
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
