@@ -7,6 +7,8 @@
 //   "IvSQ"  IndexIVFScalarQuantizer (index_io.cpp:208-215, :283-292, :439-447, :611-620)
 //   "IxPq"  IndexPQ (index_io.cpp:259-270); read as well: its older records "IxPQ" and "IxPo" (:578-596)
 //   "IxRF"  IndexRefineFlat (index_io.cpp:336-341, :645-654): header, the base index, the refine IndexFlat, k_factor
+//   "IxHe"  IndexLSH (index_io.cpp:248-258); read as well: its older record "IxHE" (:549-575).  Its rotation is the one
+//           VectorTransform record built here, "rrot" (index_io.cpp:159-175, :189-193, :391-410, :425-427)
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
 // byte identity against files the reference wrote).  Other fourccs are outside the path
 // and rejected.
@@ -18,6 +20,7 @@
 
 #include "IndexFlat.h"
 #include "IndexIVFPQ.h"
+#include "IndexLSH.h"
 #include "IndexPQ.h"
 #include "IndexScalarQuantizer.h"
 
@@ -86,6 +89,25 @@ inline void read_sq(ScalarQuantizer& sq, FILE* f) {          // read_ScalarQuant
   rvec(f, sq.trained);
 }
 
+
+// write_VectorTransform / read_VectorTransform (index_io.cpp:159-193, :391-428) of the one transform built here
+inline void write_rrot(const RandomRotationMatrix& lt, FILE* f) {
+  w1(f, fourcc("rrot"));
+  w1(f, lt.have_bias);
+  wvec(f, lt.A);
+  wvec(f, lt.b);
+  w1(f, lt.d_in); w1(f, lt.d_out); w1(f, lt.is_trained);
+}
+inline void read_rrot(RandomRotationMatrix& lt, FILE* f) {
+  uint32_t h;
+  r1(f, h);
+  FAISS_THROW_IF_NOT_MSG(h == fourcc("rrot"), "expected a random rotation");
+  r1(f, lt.have_bias);
+  rvec(f, lt.A);
+  rvec(f, lt.b);
+  r1(f, lt.d_in); r1(f, lt.d_out); r1(f, lt.is_trained);
+}
+
 }  // namespace io_detail
 
 inline void write_index(const Index* idx, FILE* f) {
@@ -100,6 +122,16 @@ inline void write_index(const Index* idx, FILE* f) {
     write_index(idxrf->base_index, f);
     write_index(&idxrf->refine_index, f);
     w1(f, idxrf->k_factor);
+  } else if (const IndexLSH* idxl = dynamic_cast<const IndexLSH*>(idx)) {
+    w1(f, fourcc("IxHe"));                     // index_io.cpp:248-258
+    write_header(idx, f);
+    w1(f, idxl->nbits);
+    w1(f, idxl->rotate_data);
+    w1(f, idxl->train_thresholds);
+    wvec(f, idxl->thresholds);
+    w1(f, idxl->bytes_per_vec);
+    write_rrot(idxl->rrot, f);
+    wvec(f, idxl->codes);
   } else if (const MultiIndexQuantizer* miq = dynamic_cast<const MultiIndexQuantizer*>(idx)) {
     w1(f, fourcc("Imiq"));
     write_header(idx, f);
@@ -191,6 +223,25 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     own.xb.swap(rf->xb);
     r1(f, idxrf->k_factor);
     return idxrf.release();
+  }
+  if (h == fourcc("IxHE") || h == fourcc("IxHe")) {      // index_io.cpp:549-575
+    std::unique_ptr<IndexLSH> idxl(new IndexLSH());
+    read_header(idxl.get(), f);
+    r1(f, idxl->nbits);
+    r1(f, idxl->rotate_data);
+    r1(f, idxl->train_thresholds);
+    rvec(f, idxl->thresholds);
+    r1(f, idxl->bytes_per_vec);
+    if (h == fourcc("IxHE")) {
+      FAISS_THROW_IF_NOT_FMT(idxl->nbits % 64 == 0, "can only read old format IndexLSH with nbits multiple of 64 (got %d)", (int)idxl->nbits);
+      idxl->bytes_per_vec *= 8;
+    }
+    read_rrot(idxl->rrot, f);
+    rvec(f, idxl->codes);
+    FAISS_THROW_IF_NOT(idxl->rrot.d_in == idxl->d && idxl->rrot.d_out == idxl->nbits);
+    FAISS_THROW_IF_NOT(idxl->codes.size() == (size_t)idxl->ntotal * idxl->bytes_per_vec);
+    idxl->codes_changed();
+    return idxl.release();
   }
   if (h == fourcc("Imiq")) {
     std::unique_ptr<MultiIndexQuantizer> miq(new MultiIndexQuantizer(2, 2, 1));

@@ -634,6 +634,67 @@ int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const f
  *   "kernel=refine_flat_kernel select=1 metric=l2 read=tile128 waves=2 trips=2 slots=128 page=32768 lds=21248" */
 int vlq_flat_last_refine_info(vlq_flat_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * LSH index: faiss::IndexLSH (IndexLSH.h, IndexLSH.cpp; "sign-bit codes plus Hamming k-NN") on the device.  A vector becomes
+ * (nbits + 7) / 8 bytes; search is the exhaustive Hamming scan of every stored code (hammings_knn, hamming.cpp:474-506).
+ *   preprocess (apply_preprocess, IndexLSH.cpp:50-81)
+ *     rotate_data      xt[j] = b[j] + sum_i A[j * d + i] * x[i]: LinearTransform::apply (VectorTransform.cpp:105-131) with A
+ *                      [nbits][d] row-major exactly as rrot.A is stored.  The reference hands this to sgemm_, whose summation
+ *                      order is the BLAS vendor's; this library's standing definition is the fmaf chain over i = 0 .. d-1
+ *                      ascending, starting from b[j] (from 0.0f without a bias), as vlq_flat_search defines its GEMM path.
+ *     otherwise        the first nbits components (d >= nbits)
+ *     train_thresholds xt[j] -= thresholds[j], one subtraction, after the transform
+ *   bits (fvecs2bitvecs, hamming.cpp:353-379): bit j = xt[j] >= 0 (-0.0f sets it, NaN does not), dimension 0 is the least
+ *     significant bit of byte 0, pad bits are zero.
+ *   search (IndexLSH.cpp:128-157): rows ascending by the total order (distance, position), distances the integer Hamming
+ *     distances as floats, padded (float)INT_MAX = 2147483648.0f / -1 (Heap.h:76-78 through IndexLSH.cpp:154-155).  The reference
+ *     keeps a max-heap per query and admits on `dis < top`: which of several codes AT the k-th distance survive depends on its
+ *     heap's layout.  So rows equal the reference's in every distance slot, and in the labels up to the order inside groups of
+ *     equal distance and the choice inside the group that straddles the k-th place (DESIGN.md sections 5 and 3.16).  The rows
+ *     depend on no tiling, slicing or paging choice.
+ * Limits: k in 1 .. VLQ_MAX_K (k > ntotal pads, ntotal == 0 gives padded rows), ntotal < 2^32 (the key's position field).
+ * Searched code widths are hammings_knn's: 4 bytes and every multiple of 8 up to 128; any other width (nbits = 100: 13 bytes)
+ * is VLQ_ERR_INVALID from the search calls (hamming.cpp:501 throws there) while add / encode / get_codes still work, as in the
+ * reference.  add / encode / search before the matrix of a rotate_data index or the thresholds of a train_thresholds index are
+ * set: VLQ_ERR_INVALID ("not trained", IndexLSH.cpp:118, :135).  Queries go to the device in pages of 32 768.  Training
+ * (IndexLSH::train, the per-bit median) is host work over vlq_lsh_apply: vlq.GpuLSH.train.  Pointers [h|d]. */
+typedef struct vlq_lsh_s* vlq_lsh_t;
+
+/* IndexLSH::IndexLSH (IndexLSH.cpp:29-42); d < nbits without rotate_data: VLQ_ERR_INVALID (:40).  No matrix is drawn here
+ * (rrot.init(5), :38, is the caller's: vlq_lsh_set_rotation) */
+int vlq_lsh_create(vlq_lsh_t* out, int device, int d, int nbits, int rotate_data, int train_thresholds);
+void vlq_lsh_destroy(vlq_lsh_t h);
+int vlq_lsh_set_stream(vlq_lsh_t h, void* hip_stream);
+/* rrot.A [nbits*d] and rrot.b [nbits] or NULL = no bias (VectorTransform.h:68-71, index_io.cpp:391-410 "rrot") [h|d] */
+int vlq_lsh_set_rotation(vlq_lsh_t h, const float* A, const float* b);
+/* IndexLSH::thresholds [nbits] (IndexLSH.h:31) [h|d]; NULL: back to untrained (vlq_lsh_apply then subtracts nothing) */
+int vlq_lsh_set_thresholds(vlq_lsh_t h, const float* t);
+/* apply_preprocess (IndexLSH.cpp:50-81): xt_out[n*nbits] [h|d].  Thresholds are subtracted once they are set; before that the
+ * rows are what IndexLSH::train sorts (:89-92) */
+int vlq_lsh_apply(vlq_lsh_t h, int64_t n, const float* x, float* xt_out);
+/* fvecs2bitvecs(apply_preprocess(x)) (IndexLSH.cpp:119-123): codes_out[n*bytes_per_vec] [h|d], nothing stored */
+int vlq_lsh_encode(vlq_lsh_t h, int64_t n, const float* x, uint8_t* codes_out);
+/* IndexLSH::add (IndexLSH.cpp:116-125): appended in input order, label of a vector = its position */
+int vlq_lsh_add(vlq_lsh_t h, int64_t n, const float* x);
+/* ready-made codes[n*bytes_per_vec] [h|d] appended as they are (IndexLSH::codes, index_io.cpp:549-575 "IxHe") */
+int vlq_lsh_add_codes(vlq_lsh_t h, int64_t n, const uint8_t* codes);
+/* IndexLSH::codes of vectors i0 .. i0+ni-1: out[ni*bytes_per_vec] [h|d] */
+int vlq_lsh_get_codes(vlq_lsh_t h, int64_t i0, int64_t ni, uint8_t* out);
+int64_t vlq_lsh_ntotal(vlq_lsh_t h);
+/* IndexLSH::reset (IndexLSH.cpp:173-176) */
+int vlq_lsh_reset(vlq_lsh_t h);
+int vlq_lsh_reserve_memory(vlq_lsh_t h, int64_t num_vecs);
+/* IndexLSH::search (IndexLSH.cpp:128-157): x[n*d], D[n*k], I[n*k] [h|d] */
+int vlq_lsh_search(vlq_lsh_t h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* hammings_knn with order = true (hamming.cpp:474-506) of ready-made query codes qcodes[n*bytes_per_vec] [h|d] */
+int vlq_lsh_search_codes(vlq_lsh_t h, int64_t n, const uint8_t* qcodes, int k, float* D, int64_t* I);
+/* Speed only, results never depend on it: queries per workgroup (0, 1, 2, 4; k > 256 always runs 1) and code slices (0 .. 64);
+ * 0 = the plan decides (csrc/hamming_plan.h) */
+int vlq_lsh_set_scan_split(vlq_lsh_t h, int query_tile, int slices);
+/* Introspection, speed only: the last scan launch as text,
+ *   "kernel=scan_hamming_kernel<2, 1, 16> Q=2 S=4 slice=250000 page=32768 lds=4368 join=1".  Synchronises the stream. */
+int vlq_lsh_last_scan_info(vlq_lsh_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

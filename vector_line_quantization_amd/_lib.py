@@ -43,6 +43,10 @@ SYMBOLS = [
     "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
     "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
     "vlq_flat_compute_distance_subset", "vlq_flat_refine", "vlq_flat_last_refine_info",
+    # LSH: sign-bit codes and Hamming k-NN (vlq_lsh_t)
+    "vlq_lsh_create", "vlq_lsh_destroy", "vlq_lsh_set_stream", "vlq_lsh_set_rotation", "vlq_lsh_set_thresholds", "vlq_lsh_apply",
+    "vlq_lsh_encode", "vlq_lsh_add", "vlq_lsh_add_codes", "vlq_lsh_get_codes", "vlq_lsh_ntotal", "vlq_lsh_reset",
+    "vlq_lsh_reserve_memory", "vlq_lsh_search", "vlq_lsh_search_codes", "vlq_lsh_set_scan_split", "vlq_lsh_last_scan_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -114,6 +118,8 @@ def lib():
         L.vlq_pq_destroy.restype = None
         L.vlq_flat_ntotal.restype = C.c_int64
         L.vlq_flat_destroy.restype = None
+        L.vlq_lsh_ntotal.restype = C.c_int64
+        L.vlq_lsh_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -868,12 +868,164 @@ class GpuFlat:
         return buf.value.decode()
 
 
+def random_rotation(d, nbits, seed=5):
+    """A random rotation [nbits][d] float32 in LinearTransform's layout (xt = A x): numpy's generator seeded with `seed`, then
+    a QR.  nbits <= d: the first nbits rows of an orthonormal d x d matrix; nbits > d: the first d columns of an orthonormal
+    nbits x nbits one.  This is A random rotation, NOT the bits of the reference's RandomRotationMatrix::init(seed): those come
+    from its own float_randn and LAPACK's sgeqrf / sorgqr.  An index that must reproduce the reference's codes takes the
+    reference's matrix as data (GpuLSH.set_rotation)."""
+    m = max(d, nbits)
+    q, _r = np.linalg.qr(np.random.default_rng(seed).standard_normal((m, m)))
+    return np.ascontiguousarray(q[:nbits, :d], dtype=np.float32)
+
+
+class GpuLSH:
+    """faiss::IndexLSH (IndexLSH.h; "LSH" of index_factory): a vector becomes the sign bits of its (optionally rotated,
+    optionally thresholded) components, search is the exhaustive Hamming scan.  Distances are the integer Hamming distances as
+    float32, ascending by (distance, position), padded 2147483648.0 / -1.  Labels are positions in the order of add.
+    With rotate_data and no set_rotation call the matrix is random_rotation(d, nbits, seed=5): a random rotation, NOT the
+    reference's bits (include/vlq_ivfpq.h, vlq_lsh_*)."""
+
+    metric = "l2"         # what a GpuRefineFlat over this index re-ranks by
+    _out = GpuIVFPQ._out
+
+    def __init__(self, d, nbits, rotate_data=True, train_thresholds=False, device=0):
+        self.d, self.nbits, self.device = d, nbits, device
+        self.rotate_data, self.train_thresholds = bool(rotate_data), bool(train_thresholds)
+        self.bytes_per_vec = (nbits + 7) // 8
+        self._h = C.c_void_p()
+        check(lib().vlq_lsh_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nbits), C.c_int(int(self.rotate_data)),
+                                   C.c_int(int(self.train_thresholds))))
+        self.is_trained = not self.train_thresholds
+        if self.rotate_data:
+            self.set_rotation(random_rotation(d, nbits, seed=5))
+
+    def _call(self, name, *args):
+        check(getattr(lib(), "vlq_lsh_" + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_lsh_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # --- state ------------------------------------------------------------
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_rotation(self, A, b=None):
+        """rrot.A [nbits][d] and rrot.b [nbits] (None: no bias)"""
+        pa, _a = _ptr(A, np.float32)
+        pb, _b = _ptr(b, np.float32)
+        self._call("set_rotation", pa, pb)
+
+    def set_thresholds(self, t):
+        """IndexLSH::thresholds [nbits]; None: back to untrained"""
+        pt, _t = _ptr(t, np.float32)
+        self._call("set_thresholds", pt)
+        self.is_trained = t is not None or not self.train_thresholds
+
+    def train(self, x):
+        """IndexLSH::train (IndexLSH.cpp:85-113): the rotation runs on the device, the per-bit median is taken here -- the sorted
+        column's element n/2 for odd n, (x[n/2-1] + x[n/2]) / 2 in float32 for even n.  Returns the thresholds."""
+        if not self.train_thresholds:
+            self.is_trained = True
+            return None
+        self.set_thresholds(None)
+        xt = self.apply(x)
+        xt = np.sort(xt.cpu().numpy() if _is_torch(xt) else xt, axis=0)
+        n = xt.shape[0]
+        if n % 2 == 1:
+            t = xt[n // 2].copy()
+        else:
+            t = ((xt[n // 2 - 1] + xt[n // 2]) / np.float32(2)).astype(np.float32)
+        self.set_thresholds(t)
+        return t
+
+    def apply(self, x, out=None):
+        """apply_preprocess: [n][nbits] float32 (thresholds are subtracted once they are set)"""
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        out = self._out(out, (n, self.nbits), np.float32, x)
+        self._call("apply", C.c_int64(n), px, _out_ptr(out, np.float32)[0])
+        return out
+
+    def encode(self, x):
+        """the codes [n][bytes_per_vec] add would store; nothing is stored"""
+        px, _a = _ptr(x, np.float32)
+        codes = np.empty((x.shape[0], self.bytes_per_vec), np.uint8)
+        self._call("encode", C.c_int64(x.shape[0]), px, codes.ctypes.data_as(C.c_void_p))
+        return codes
+
+    def add(self, x):
+        px, _a = _ptr(x, np.float32)
+        self._call("add", C.c_int64(x.shape[0]), px)
+
+    def add_codes(self, codes):
+        """ready-made codes [n][bytes_per_vec] uint8, appended as they are"""
+        if codes.shape[1] != self.bytes_per_vec:
+            raise ValueError("codes of %d bytes for an index of %d" % (codes.shape[1], self.bytes_per_vec))
+        pc, _c = _ptr(codes, np.uint8)
+        self._call("add_codes", C.c_int64(codes.shape[0]), pc)
+
+    def get_codes(self, i0=0, ni=None):
+        """stored codes i0 .. i0 + ni - 1, [ni][bytes_per_vec] uint8"""
+        ni = self.ntotal - i0 if ni is None else ni
+        out = np.empty((ni, self.bytes_per_vec), np.uint8)
+        self._call("get_codes", C.c_int64(i0), C.c_int64(ni), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_lsh_ntotal(self._h))
+
+    def reset(self):
+        self._call("reset")
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    # --- search -----------------------------------------------------------
+    def search(self, x, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def search_codes(self, qcodes, k, D=None, I=None):
+        """hammings_knn of ready-made query codes [n][bytes_per_vec] uint8"""
+        n = qcodes.shape[0]
+        if qcodes.shape[1] != self.bytes_per_vec:
+            raise ValueError("codes of %d bytes for an index of %d" % (qcodes.shape[1], self.bytes_per_vec))
+        pq, _a = _ptr(qcodes, np.uint8)
+        D = self._out(D, (n, k), np.float32, qcodes)
+        I = self._out(I, (n, k), np.int64, qcodes)
+        self._call("search_codes", C.c_int64(n), pq, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def scan_split(self, query_tile=0, slices=0):
+        """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
+        self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
+
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
 VLQ_MAX_K = 1024      # include/vlq_ivfpq.h
 
 
 class GpuRefineFlat:
     """faiss::IndexRefineFlat (IndexFlat.h:103-140): a base index whose shortlist of k * k_factor candidates is re-scored
-    exactly against the uncompressed vectors kept beside it.  base: GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ or GpuFlat; the
+    exactly against the uncompressed vectors kept beside it.  base: GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat or GpuLSH; the
     refine store is a GpuFlat of the base's d and metric.  A base label must be a position in the store: add() keeps the two in
     step (IVF bases get the sequential ids ntotal .. ntotal + n - 1); an index whose lists were set with ids 0 .. ntotal - 1
     gets its store from set_store().  The base and the store share one stream of this object's (set_stream replaces it), so the
@@ -881,8 +1033,8 @@ class GpuRefineFlat:
 
     def __init__(self, base):
         import torch
-        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat)):
-            raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ or GpuFlat, got %s" % type(base).__name__)
+        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat, GpuLSH)):
+            raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat or GpuLSH, got %s" % type(base).__name__)
         self.base = base
         self.d, self.metric, self.device = base.d, base.metric, base.device
         self.k_factor = 1.0
