@@ -1,5 +1,6 @@
-// faiss::ScalarQuantizer (IndexScalarQuantizer.h:30-79) and faiss::IndexIVFScalarQuantizer (IndexScalarQuantizer.h:129-155,
-// IndexScalarQuantizer.cpp:805-1002; "IVFx,SQ8" / "IVFx,SQ4" of index_factory) over the MI355X library.
+// faiss::ScalarQuantizer (IndexScalarQuantizer.h:30-79), faiss::IndexScalarQuantizer (IndexScalarQuantizer.h:82-120,
+// IndexScalarQuantizer.cpp:698-802; "SQ8" / "SQ4" of index_factory) and faiss::IndexIVFScalarQuantizer
+// (IndexScalarQuantizer.h:129-155, IndexScalarQuantizer.cpp:805-1002; "IVFx,SQ8" / "IVFx,SQ4") over the MI355X library.
 //
 // ScalarQuantizer is host code with the reference's fields: train (RS_minmax only; the three other range statistics are not
 // built and throw a FaissException that says so), compute_codes and decode, each float operation in the reference's order
@@ -13,8 +14,15 @@
 // after a change (sync_(), as IndexIVFFlat of IndexIVF.h does).  add_with_ids assigns through the quantizer and encodes on the
 // host; search runs on the device (csrc/scan_sq.hip).
 //
-// The non-IVF faiss::IndexScalarQuantizer ("IxSQ", IndexScalarQuantizer.h:82-120) is not built, and neither class is added to
-// the interposer (integration/reference_interposer.cpp).
+// IndexScalarQuantizer ("IxSQ") keeps the reference's fields sq, codes and code_size.  train, add (sq.compute_codes), reset,
+// reconstruct and reconstruct_n are host code through sq; the host vector `codes` stays authoritative -- what write_index
+// writes -- and is mirrored to a vlq_sq_t before the first search after a change; search runs on the device
+// (csrc/scan_sqflat.hip).  The reference never reorders its heap in this search (maxheap_reorder / minheap_reorder are called
+// in search_with_probes_*, IndexScalarQuantizer.cpp:917, :955, not in :727-781), so its rows come back in heap order; here
+// they come back sorted: distance ascending (inner product: descending), then position ascending, padded FLT_MAX / -1
+// (inner product: -FLT_MAX / -1).  The same results, slot by slot after sorting.
+//
+// None of the classes is added to the interposer (integration/reference_interposer.cpp).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -136,6 +144,80 @@ struct ScalarQuantizer {
   void check_trained_() const {
     FAISS_THROW_IF_NOT_MSG(trained.size() == (uniform() ? (size_t)2 : 2 * d), "ScalarQuantizer: not trained");
   }
+};
+
+/// IndexScalarQuantizer.h:82-120
+struct IndexScalarQuantizer : Index {
+  ScalarQuantizer sq;            ///< used to encode the vectors
+  std::vector<uint8_t> codes;    ///< ntotal * code_size, the authoritative copy (what write_index writes)
+  size_t code_size;
+
+  /// device the index lives on (set before search)
+  int device = 0;
+
+  /// :698-706
+  IndexScalarQuantizer(int d, ScalarQuantizer::QuantizerType qtype, MetricType metric = METRIC_L2) : Index(d, metric), sq(d, qtype) {
+    is_trained = false;
+    code_size = sq.code_size;
+  }
+  IndexScalarQuantizer() : IndexScalarQuantizer(0, ScalarQuantizer::QT_8bit) {}   // :709-711
+  ~IndexScalarQuantizer() override { if (h_) vlq_sq_destroy(h_); }
+  IndexScalarQuantizer(const IndexScalarQuantizer&) = delete;
+  IndexScalarQuantizer& operator=(const IndexScalarQuantizer&) = delete;
+
+  void train(idx_t n, const float* x) override {   // :713-717
+    sq.train(n, x);
+    is_trained = true;
+    tdirty_ = true;
+  }
+  void add(idx_t n, const float* x) override {     // :719-725
+    FAISS_THROW_IF_NOT(is_trained);
+    codes.resize((size_t)(n + ntotal) * code_size);
+    sq.compute_codes(x, &codes[(size_t)ntotal * code_size], n);
+    ntotal += n;
+    cdirty_ = true;
+  }
+  /// :727-781 on the device; rows sorted (see the header comment)
+  void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override {
+    FAISS_THROW_IF_NOT(is_trained);
+    FAISS_THROW_IF_NOT_MSG(metric_type == METRIC_L2 || metric_type == METRIC_INNER_PRODUCT, "unknown metric");
+    FAISS_THROW_IF_NOT(sq.d == (size_t)d && code_size == sq.code_size && codes.size() == (size_t)ntotal * code_size);
+    if (n == 0) return;
+    if (!h_) {
+      VLQ_CHECK(vlq_sq_create(&h_, device, d, (int)sq.qtype, (int)metric_type));
+      tdirty_ = cdirty_ = true;
+    }
+    if (tdirty_) {
+      VLQ_CHECK(vlq_sq_set_trained(h_, sq.trained.data(), (int)sq.trained.size()));
+      tdirty_ = false;
+    }
+    if (cdirty_) {
+      VLQ_CHECK(vlq_sq_set_codes(h_, codes.data(), ntotal));
+      cdirty_ = false;
+    }
+    VLQ_CHECK(vlq_sq_search(h_, n, x, (int)k, distances, (int64_t*)labels));
+  }
+  void reset() override {   // :783-787
+    codes.clear();
+    ntotal = 0;
+    cdirty_ = true;
+  }
+  void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override {   // :789-797
+    FAISS_THROW_IF_NOT(ni == 0 || (i0 >= 0 && i0 + ni <= ntotal));
+    if (ni > 0) sq.decode(&codes[(size_t)i0 * code_size], recons, ni);
+  }
+  void reconstruct(idx_t key, float* recons) const override { reconstruct_n(key, 1, recons); }   // :799-802
+
+  /// after writing codes / sq / ntotal directly (read_index, a copy from another index): d, the quantizer type and the metric
+  /// are fixed at the handle's creation, so it is made again
+  void codes_changed() {
+    if (h_) { vlq_sq_destroy(h_); h_ = nullptr; }
+    tdirty_ = cdirty_ = true;
+  }
+
+ protected:
+  mutable vlq_sq_t h_ = nullptr;
+  mutable bool tdirty_ = true, cdirty_ = true;
 };
 
 struct IndexIVFScalarQuantizer : IndexIVF {

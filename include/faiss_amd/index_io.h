@@ -5,6 +5,7 @@
 //   "IxF2"  IndexFlatL2            "Imiq"  MultiIndexQuantizer        "IvPQ"  IndexIVFPQ
 //   "IvFl"  IndexIVFFlat (index_io.cpp:276-283, :597-603)
 //   "IvSQ"  IndexIVFScalarQuantizer (index_io.cpp:208-215, :283-292, :439-447, :611-620)
+//   "IxSQ"  IndexScalarQuantizer (index_io.cpp:271-275, :604-610): header, the ScalarQuantizer, the codes
 //   "IxPq"  IndexPQ (index_io.cpp:259-270); read as well: its older records "IxPQ" and "IxPo" (:578-596)
 //   "IxRF"  IndexRefineFlat (index_io.cpp:336-341, :645-654): header, the base index, the refine IndexFlat, k_factor
 //   "IxHe"  IndexLSH (index_io.cpp:248-258); read as well: its older record "IxHE" (:549-575).  Its rotation is the one
@@ -144,6 +145,11 @@ inline void write_index(const Index* idx, FILE* f) {
     w1(f, idxp->search_type);
     w1(f, idxp->encode_signs);
     w1(f, idxp->polysemous_ht);
+  } else if (const IndexScalarQuantizer* idxs = dynamic_cast<const IndexScalarQuantizer*>(idx)) {
+    w1(f, fourcc("IxSQ"));                     // index_io.cpp:271-275
+    write_header(idx, f);
+    write_sq(idxs->sq, f);
+    wvec(f, idxs->codes);
   } else if (const IndexIVFFlat* ivfl = dynamic_cast<const IndexIVFFlat*>(idx)) {
     w1(f, fourcc("IvFl"));                     // index_io.cpp:276-283
     write_header(idx, f);                      // write_ivf_header, index_io.cpp:226-238
@@ -265,6 +271,16 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     idxp->quantizer_changed();
     idxp->codes_changed();
     return idxp.release();
+  }
+  if (h == fourcc("IxSQ")) {                   // index_io.cpp:604-610
+    std::unique_ptr<IndexScalarQuantizer> idxs(new IndexScalarQuantizer());
+    read_header(idxs.get(), f);
+    read_sq(idxs->sq, f);
+    rvec(f, idxs->codes);
+    idxs->code_size = idxs->sq.code_size;
+    FAISS_THROW_IF_NOT(idxs->codes.size() == (size_t)idxs->ntotal * idxs->code_size);
+    idxs->codes_changed();
+    return idxs.release();
   }
   if (h == fourcc("IvFl")) {                   // index_io.cpp:597-603
     std::unique_ptr<IndexIVFFlat> iv(new IndexIVFFlat());

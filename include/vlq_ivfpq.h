@@ -562,6 +562,66 @@ int vlq_pq_set_scan_split(vlq_pq_t h, int query_tile, int slices);
  *   "kernel=scan_pq_kernel<4, 1, group4, none, 16> Q=4 S=2 slice=500000 lds=73744 join=1".  Synchronises the stream. */
 int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap);
 
+/* ---- Flat scalar-quantizer index: every stored code is decoded and compared with every query (faiss::IndexScalarQuantizer,
+ * IndexScalarQuantizer.h:82-120, IndexScalarQuantizer.cpp:698-802; what index_factory builds for "SQ8" / "SQ4",
+ * AutoTune.cpp:721-737; the "IxSQ" record of index_io.cpp:271-275, :604-610).  A handle of its own; the scan is
+ * csrc/scan_sqflat.hip under the plan of csrc/sqflat_plan.h: a grid of (query tile) x (code slice), a code's component decoded
+ * once and scored for the tile's queries, slices joined by the total order (distance, scan position).  Labels are scan
+ * positions 0 .. ntotal-1.
+ *   search  (:727-781) per query a heap of k slots, all ntotal codes in order, compute_distance_L2 / compute_distance_IP with
+ *           SimilarityL2(x) / SimilarityIP(x, 0), admitted on strict `accu < simi[0]` (L2) / `accu > simi[0]` (inner product).
+ *           The float operations are those of the IVF index above (decode with the AVX codec's multiply by the rounded
+ *           reciprocal and eight accumulators joined as result_8 when d % 8 == 0; a true division and one accumulator over
+ *           ascending i otherwise), with y the query itself -- no residual -- and accu0 the constant 0: under inner product
+ *           and d % 8 == 0 the result is still (0.f + lo) + hi.
+ *   rows    The reference never reorders its heap here (maxheap_reorder / minheap_reorder are called in search_with_probes_*,
+ *           :917, :955, not in IndexScalarQuantizer::search): its rows come back in heap order.  This library returns them
+ *           sorted by its total order -- distance ascending (inner product: descending), then position ascending -- padded
+ *           FLT_MAX / -1 (inner product: -FLT_MAX / -1).  Parity is stated on sorted rows: the distances equal the reference's
+ *           bit for bit in every slot, the labels up to the heap's choice inside a group of equal distances that crosses the
+ *           k-th place.
+ *   add / encode   encode_vector of x itself (:446-455, :520-529, :719-725); reconstruct: decode_vector (:457-462, :531-536,
+ *           :789-797), the scalar codec (c + 0.5f) / den by a true division whatever d is.
+ * Errors: search / add / encode / reconstruct before vlq_sq_set_trained: VLQ_ERR_INVALID (FAISS_THROW_IF_NOT (is_trained), :721,
+ * :736); a shape the plan refuses (the tile's queries, the range and the turn tiles beyond 160 KB of LDS: d above about 10 000;
+ * k > VLQ_MAX_K; ntotal >= 2^32): VLQ_ERR_UNSUPPORTED, the plan's reason is in the message and in vlq_sq_last_scan_info; a bad
+ * qtype or metric: VLQ_ERR_INVALID.  Only RS_minmax training is stated (vlq.GpuSQ.train, on the host).  Pointers marked [h|d]
+ * as above. */
+typedef struct vlq_sq_s* vlq_sq_t;
+
+/* IndexScalarQuantizer::IndexScalarQuantizer (:698-706).  qtype: ScalarQuantizer::QuantizerType 0..3; metric: 0 = inner product,
+ * 1 = L2 */
+int vlq_sq_create(vlq_sq_t* out, int device, int d, int qtype, int metric);
+void vlq_sq_destroy(vlq_sq_t h);
+int vlq_sq_set_stream(vlq_sq_t h, void* hip_stream);
+/* ScalarQuantizer::trained (vmin[d] then vdiff[d]; vmin, vdiff for the uniform types): trained[count] host floats.  A vdiff that
+ * is zero, negative or not finite: VLQ_ERR_INVALID.  get_trained: out[count] host floats. */
+int vlq_sq_set_trained(vlq_sq_t h, const float* trained, int count);
+int vlq_sq_get_trained(vlq_sq_t h, float* out, int count);
+int vlq_sq_code_size(vlq_sq_t h);
+/* IndexScalarQuantizer::codes (index_io.cpp:608): codes[n*code_size] [h|d]; replaces the stored codes */
+int vlq_sq_set_codes(vlq_sq_t h, const uint8_t* codes, int64_t n);
+/* IndexScalarQuantizer::add (:719-725): sq.compute_codes on the device, appended in input order.  x[n*d] [h|d] */
+int vlq_sq_add(vlq_sq_t h, int64_t n, const float* x);
+/* sq.compute_codes (:674-683), nothing stored: codes_out[n*code_size] [h|d] */
+int vlq_sq_encode(vlq_sq_t h, int64_t n, const float* x, uint8_t* codes_out);
+/* codes i0 .. i0+ni-1 in scan order: out[ni*code_size] [h|d] */
+int vlq_sq_get_codes(vlq_sq_t h, int64_t i0, int64_t ni, uint8_t* out);
+/* IndexScalarQuantizer::reconstruct_n (:789-797): x_out[ni*d] [h|d]; i0 .. i0+ni beyond ntotal: VLQ_ERR_INVALID */
+int vlq_sq_reconstruct(vlq_sq_t h, int64_t i0, int64_t ni, float* x_out);
+int64_t vlq_sq_ntotal(vlq_sq_t h);
+/* IndexScalarQuantizer::reset (:783-787) */
+int vlq_sq_reset(vlq_sq_t h);
+int vlq_sq_reserve_memory(vlq_sq_t h, int64_t num_vecs);
+/* IndexScalarQuantizer::search (:727-781).  x[n*d], D[n*k], I[n*k] [h|d] */
+int vlq_sq_search(vlq_sq_t h, int64_t n, const float* x, int k, float* D, int64_t* I);
+/* Speed only, results never depend on it: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides */
+int vlq_sq_set_scan_split(vlq_sq_t h, int query_tile, int slices);
+/* Introspection, speed only: the last scan launch as text,
+ *   "kernel=scan_sqflat_kernel<4, 1, L2, 8, nonuniform, order8> read=tile128 Q=4 S=2 slice=500000 lds=41472 join=1",
+ * or "kernel=none why=..." after a search the plan refused.  Synchronises the stream. */
+int vlq_sq_last_scan_info(vlq_sq_t h, char* buf, int cap);
+
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Flat exact k-NN index: faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (IndexFlat.cpp:30-56, :118-121; gpu::GpuIndexFlat) on the
  * device.  The vectors are stored as rows of 4 * d bytes with their squared norms beside them; add appends on the device and

@@ -39,6 +39,10 @@ SYMBOLS = [
     "vlq_pq_create", "vlq_pq_destroy", "vlq_pq_set_stream", "vlq_pq_set_centroids", "vlq_pq_set_codes", "vlq_pq_add", "vlq_pq_encode",
     "vlq_pq_get_codes", "vlq_pq_ntotal", "vlq_pq_reset", "vlq_pq_reserve_memory", "vlq_pq_set_search_type", "vlq_pq_search",
     "vlq_pq_query_tables", "vlq_pq_query_codes", "vlq_pq_stats", "vlq_pq_set_scan_split", "vlq_pq_last_scan_info",
+    # flat scalar quantizer (vlq_sq_t)
+    "vlq_sq_create", "vlq_sq_destroy", "vlq_sq_set_stream", "vlq_sq_set_trained", "vlq_sq_get_trained", "vlq_sq_code_size",
+    "vlq_sq_set_codes", "vlq_sq_add", "vlq_sq_encode", "vlq_sq_get_codes", "vlq_sq_reconstruct", "vlq_sq_ntotal", "vlq_sq_reset",
+    "vlq_sq_reserve_memory", "vlq_sq_search", "vlq_sq_set_scan_split", "vlq_sq_last_scan_info",
     # flat exact k-NN (vlq_flat_t)
     "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
     "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
@@ -116,6 +120,8 @@ def lib():
         L.vlq_ivfsq_destroy.restype = None
         L.vlq_pq_ntotal.restype = C.c_int64
         L.vlq_pq_destroy.restype = None
+        L.vlq_sq_ntotal.restype = C.c_int64
+        L.vlq_sq_destroy.restype = None
         L.vlq_flat_ntotal.restype = C.c_int64
         L.vlq_flat_destroy.restype = None
         L.vlq_lsh_ntotal.restype = C.c_int64

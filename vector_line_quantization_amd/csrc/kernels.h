@@ -9,6 +9,7 @@
 #include "pq_plan.h"
 #include "refine_flat_plan.h"
 #include "scan_plan.h"
+#include "sqflat_plan.h"
 
 namespace vlq {
 
@@ -363,6 +364,28 @@ void launch_pq_table_argmin(const float* tabs, int64_t n, int M, int ksub, uint8
 void launch_pq_sdc_table(const float* cent, int M, int ksub, int dsub, float* sdc, hipStream_t s);
 void launch_pq_sdc_gather(const float* sdc, const uint8_t* qcodes, int64_t n, int M, int ksub, float* tabs, hipStream_t s);
 void launch_iota(int64_t* out, int64_t n, int64_t base, hipStream_t s);       // out[i] = base + i
+
+// Flat scalar-quantizer index (faiss::IndexScalarQuantizer::search, IndexScalarQuantizer.cpp:727-781; scan_sqflat.hip): the
+// exhaustive scan of `codes` [ntotal][sq_code_size(d, qtype)] for nq queries [nq][d].  trained: ScalarQuantizer::trained on the
+// device (vmin[d], vdiff[d]; two floats for the uniform types).  Grid, tile, slices, operation order, read path and LDS are
+// plan_sqflat_scan's decision (sqflat_plan.h); the caller copies its S and slice_len here.  part: [nq][S][k] keys of scratch
+// when S > 1.  Rows: (distance, position) ascending, padded FLT_MAX / -1; inner product: descending, -FLT_MAX / -1.  false: not
+// built.
+struct SqFlatScanArgs {
+    const uint8_t* codes;
+    const float* queries;
+    const float* trained;
+    float* D;
+    int64_t* I;
+    unsigned long long* part;
+    int64_t nq, ntotal, slice_len;
+    int d, k, S;
+};
+bool launch_scan_sqflat(const SqFlatScanArgs& a, const SqFlatPlan& P, bool inner_product, hipStream_t s);
+// encode_vector of x itself (IndexScalarQuantizer.cpp:446-455, :520-529, :719-725): codes[n][code_size]
+void launch_sqflat_encode(const float* x, int64_t n, int d, const float* trained, int qtype, uint8_t* codes, hipStream_t s);
+// decode_vector (:457-462, :531-536, :789-797), the scalar codec whatever d is: x[n][d]
+void launch_sqflat_decode(const uint8_t* codes, int64_t n, int d, const float* trained, int qtype, float* x, hipStream_t s);
 
 // Flat exact k-NN (faiss::IndexFlat::search, IndexFlat.cpp:30-56, utils.cpp:726-946; scan_knn.hip): one page (nq <= P.page) of
 // queries xq [nq][d] against the stored vectors xb [ntotal][d].  Path, route, row tile, slices, chunk and LDS are plan_knn's

@@ -26,48 +26,13 @@
 #include "kernels.h"
 #include "scan_common.cuh"
 #include "scan16_common.cuh"
+#include "sq_codec.cuh"
 #include "sq_plan.h"
 #include "wave_topk.cuh"
 
 namespace vlq {
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));      // a native 16-byte vector: one dwordx4 / ds b128 access
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-struct SqTile { v4u r[8]; };
-
-// tile (rows j0 .. j0+63, bytes c0 .. c0+127) of the list at `base`: instruction i fetches rows 8i .. 8i+7, lane l the piece
-// l % 8 of row 8i + l / 8.  Rows are clamped to the list and pieces to the row (code_size >= 16 on this path), so nothing
-// outside the list is touched; what a clamped lane fetches is never read back.
-__device__ __forceinline__ SqTile sq_tile_load(const uint8_t* __restrict__ base, uint32_t j0, int c0, uint32_t len, int code_size, int lane) {
-    SqTile t;
-    const int col = min(c0 + (lane & 7) * 16, code_size - 16);
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const uint32_t row = min(j0 + (uint32_t)(i * 8 + (lane >> 3)), len - 1);
-        t.r[i] = *reinterpret_cast<const v4u*>(base + (size_t)row * code_size + col);
-    }
-    return t;
-}
-
-// the range of the quantizer as the kernel reads it: per-dimension arrays in LDS, or the two floats of a uniform type
-struct SqRange { const float* vmin; const float* vdiff; float vmin0, vdiff0; };
-
-template <int BITS, bool ORDER8>
-__device__ __forceinline__ float sq_decode(uint32_t c, float vmin, float vdiff) {
-    constexpr float den = BITS == 8 ? 255.f : 15.f;
-    const float f = __fadd_rn((float)c, 0.5f);
-    const float xi = ORDER8 ? __fmul_rn(f, 1.f / den) : __fdiv_rn(f, den);
-    return __fadd_rn(vmin, __fmul_rn(xi, vdiff));
-}
-
-template <bool IP>
-__device__ __forceinline__ float sq_accumulate(float acc, float y, float rec) {
-    if constexpr (IP) return __fadd_rn(acc, __fmul_rn(y, rec));
-    const float tmp = __fsub_rn(y, rec);
-    return __fadd_rn(acc, __fmul_rn(tmp, tmp));
-}
 
 // components i0 .. i0+7 (i0 % 8 == 0) of one code into the eight accumulators.  8 bits: the bytes of w0, w1; 4 bits: the
 // nibbles of w0, low nibble first (component i in byte i / 2, :92, :98-105).
@@ -106,15 +71,6 @@ __device__ __forceinline__ void sq_unit16(const v4u u, const float* sy, const Sq
         sq_group8<IP, 4, UNIFORM>(u.z, 0u, sy, R, i0 + 16, a);
         sq_group8<IP, 4, UNIFORM>(u.w, 0u, sy, R, i0 + 24, a);
     }
-}
-
-// result_8 (:165-172, :216-224)
-template <bool IP>
-__device__ __forceinline__ float sq_join8(const float (&a)[8], float accu0) {
-    const float lo = __fadd_rn(__fadd_rn(a[0], a[1]), __fadd_rn(a[2], a[3]));
-    const float hi = __fadd_rn(__fadd_rn(a[4], a[5]), __fadd_rn(a[6], a[7]));
-    if constexpr (IP) return __fadd_rn(__fadd_rn(accu0, lo), hi);
-    return __fadd_rn(lo, hi);
 }
 
 }  // namespace

@@ -767,6 +767,127 @@ class GpuPQ:
         return buf.value.decode()
 
 
+class GpuSQ:
+    """faiss::IndexScalarQuantizer (IndexScalarQuantizer.h:82-120; "SQ8" / "SQ4" of index_factory): every stored code of 8 or 4
+    bits per component is decoded and compared with every query.  qtype as for GpuIVFSQ.  The reference leaves its rows in
+    heap order (it never reorders the heap in this search); here they come back sorted: metric "l2": ascending distances, then
+    ascending positions, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are scan
+    positions (include/vlq_ivfpq.h, vlq_sq_*)."""
+
+    METRICS = GpuIVFPQ.METRICS
+    QTYPES = GpuIVFSQ.QTYPES
+    _out = GpuIVFPQ._out
+
+    def __init__(self, d, qtype, device=0, metric="l2"):
+        self.d, self.device = d, device
+        self._h = C.c_void_p()
+        if metric not in self.METRICS:
+            raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
+        qt = self.QTYPES.get(qtype, qtype)
+        self.metric, self.qtype = metric, int(qt)
+        check(lib().vlq_sq_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.qtype), C.c_int(self.METRICS[metric])))
+        self.uniform = self.qtype >= 2
+        self.bits = 8 if self.qtype in (0, 2) else 4
+        self.code_size = int(lib().vlq_sq_code_size(self._h))
+
+    def _call(self, name, *args):
+        check(getattr(lib(), "vlq_sq_" + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().vlq_sq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_trained(self, trained):
+        """ScalarQuantizer::trained: vmin[d] then vdiff[d] (two floats for the uniform types), host floats"""
+        t = np.ascontiguousarray(np.asarray(trained, dtype=np.float32).ravel())
+        self._call("set_trained", t.ctypes.data_as(C.c_void_p), C.c_int(t.size))
+
+    @property
+    def trained(self):
+        t = np.empty(2 if self.uniform else 2 * self.d, np.float32)
+        self._call("get_trained", t.ctypes.data_as(C.c_void_p), C.c_int(t.size))
+        return t
+
+    def train(self, x):
+        """IndexScalarQuantizer::train (IndexScalarQuantizer.cpp:713-717) with the constructor's RS_minmax, rangestat_arg 0
+        (:270-286, :369-392): the minima / maxima of x itself, taken in float32 on the host."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if self.uniform:
+            vmin, vmax = x.min(), x.max()
+        else:
+            vmin, vmax = x.min(axis=0), x.max(axis=0)
+        self.set_trained(np.concatenate([np.atleast_1d(vmin), np.atleast_1d((vmax - vmin).astype(np.float32))]))
+
+    def set_codes(self, codes):
+        """IndexScalarQuantizer::codes [ntotal][code_size] uint8; replaces the stored codes"""
+        p, _k = _ptr(codes, np.uint8)
+        self._call("set_codes", p, C.c_int64(codes.shape[0]))
+
+    def add(self, x):
+        px, _a = _ptr(x, np.float32)
+        self._call("add", C.c_int64(x.shape[0]), px)
+
+    def encode(self, x):
+        """the codes [n][code_size] add would store; nothing is stored"""
+        px, _a = _ptr(x, np.float32)
+        codes = np.empty((x.shape[0], self.code_size), np.uint8)
+        self._call("encode", C.c_int64(x.shape[0]), px, codes.ctypes.data_as(C.c_void_p))
+        return codes
+
+    def codes(self, i0=0, n=None):
+        """stored codes i0 .. i0 + n - 1 in scan order, [n][code_size] uint8"""
+        n = self.ntotal - i0 if n is None else n
+        out = np.empty((n, self.code_size), np.uint8)
+        self._call("get_codes", C.c_int64(i0), C.c_int64(n), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def reconstruct_n(self, i0=0, n=None, out=None):
+        """IndexScalarQuantizer::reconstruct_n: the decoded vectors i0 .. i0 + n - 1, [n][d] float32 (out: a numpy array or a
+        torch tensor to fill)"""
+        n = self.ntotal - i0 if n is None else n
+        if out is None:
+            out = np.empty((n, self.d), np.float32)
+        self._call("reconstruct", C.c_int64(i0), C.c_int64(n), _out_ptr(out, np.float32)[0])
+        return out
+
+    @property
+    def ntotal(self):
+        return int(lib().vlq_sq_ntotal(self._h))
+
+    def reset(self):
+        self._call("reset")
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    def search(self, x, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def set_scan_split(self, query_tile=0, slices=0):
+        """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
+        self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
+
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
 class GpuFlat:
     """faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (gpu::GpuIndexFlat): the exact brute-force index.  metric "l2": ascending
     squared distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are positions in
@@ -1025,7 +1146,7 @@ VLQ_MAX_K = 1024      # include/vlq_ivfpq.h
 
 class GpuRefineFlat:
     """faiss::IndexRefineFlat (IndexFlat.h:103-140): a base index whose shortlist of k * k_factor candidates is re-scored
-    exactly against the uncompressed vectors kept beside it.  base: GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat or GpuLSH; the
+    exactly against the uncompressed vectors kept beside it.  base: GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat or GpuLSH; the
     refine store is a GpuFlat of the base's d and metric.  A base label must be a position in the store: add() keeps the two in
     step (IVF bases get the sequential ids ntotal .. ntotal + n - 1); an index whose lists were set with ids 0 .. ntotal - 1
     gets its store from set_store().  The base and the store share one stream of this object's (set_stream replaces it), so the
@@ -1033,8 +1154,8 @@ class GpuRefineFlat:
 
     def __init__(self, base):
         import torch
-        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat, GpuLSH)):
-            raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuFlat or GpuLSH, got %s" % type(base).__name__)
+        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat, GpuLSH)):
+            raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat or GpuLSH, got %s" % type(base).__name__)
         self.base = base
         self.d, self.metric, self.device = base.d, base.metric, base.device
         self.k_factor = 1.0
