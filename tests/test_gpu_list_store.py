@@ -6,7 +6,9 @@ for EVERY list when one list of an add overflows, length after reclaim_memory, n
 count is asserted, not only its second call.  A search after the adds must return, bit for bit, the rows of a fresh index
 that got the model through set_lists: that ties the store to what the scans read.
 The bytes a row is stored as come from the kind's own encode call (for the refine codes, which have none: from one add of the
-rows to a scratch index, read back by id); where they go, in which order and under which id is the model's."""
+rows to a scratch index, read back by id); where they go, in which order and under which id is the model's.
+The geometry -- d, the number of lists, the code width, the side bytes -- is a parameter (Geometry): this file runs the small
+one (5 lists of at most about 20 rows), tests/test_gpu_list_growth.py the ones that reach the relayout kernel's other paths."""
 import numpy as np
 import pytest
 
@@ -14,38 +16,54 @@ import vector_line_quantization_amd as vlq
 
 pytestmark = pytest.mark.gpu
 
-D_, NLIST, M_, NEDGE, NLAMBDA, MR, NBITS_R, K, NQ = 8, 5, 2, 2, 16, 2, 4, 5, 7
 KINDS = ("ivfpq", "ivfpqr", "ivfflat", "ivfsq", "vlq")
-_world = {}
 
 
-def world():
-    if not _world:
-        rng = np.random.RandomState(77)
-        _world["coarse"] = (4 * rng.randn(NLIST, D_)).astype(np.float32)
-        _world["pq"] = (0.5 * rng.randn(M_, 256, D_ // M_)).astype(np.float32)
-        _world["rpq"] = (0.1 * rng.randn(MR, 1 << NBITS_R, D_ // MR)).astype(np.float32)
-        _world["lambda"] = np.linspace(0.0, 1.0, NLAMBDA).astype(np.float32)
-        _world["train"] = near(rng, rng.randint(0, NLIST, 64))
-        _world["xq"] = near(rng, rng.randint(0, NLIST, NQ))
-    return _world
+class Geometry:
+    """What the list store sees of an index: d, the coarse lists (a VLQ index has nedge lines per list), the PQ code width M
+    (8 bits), the refine codes (mr bytes of nbits_r bits), the scalar quantizer's type.  The trained state is seeded."""
+
+    def __init__(self, d=8, nlist=5, M=2, nedge=2, nlambda=16, mr=2, nbits_r=4, qtype="8bit", k=5, nq=7, seed=77):
+        self.d, self.nlist, self.M, self.nedge, self.nlambda = d, nlist, M, nedge, nlambda
+        self.mr, self.nbits_r, self.qtype, self.k, self.nq, self.seed = mr, nbits_r, qtype, k, nq, seed
+        self._world = {}
+
+    def world(self):
+        w = self._world
+        if not w:
+            rng = np.random.RandomState(self.seed)
+            w["coarse"] = (4 * rng.randn(self.nlist, self.d)).astype(np.float32)
+            w["pq"] = (0.5 * rng.randn(self.M, 256, self.d // self.M)).astype(np.float32)
+            w["rpq"] = (0.1 * rng.randn(self.mr, 1 << self.nbits_r, self.d // self.mr)).astype(np.float32)
+            w["lambda"] = np.linspace(0.0, 1.0, self.nlambda).astype(np.float32)
+            w["train"] = near(rng, rng.randint(0, self.nlist, 64), self)
+            w["xq"] = near(rng, rng.randint(0, self.nlist, self.nq), self)
+        return w
 
 
-def near(rng, cells):
+BASE = Geometry()
+D_, NLIST, M_, NEDGE, NLAMBDA, MR, NBITS_R, K, NQ = BASE.d, BASE.nlist, BASE.M, BASE.nedge, BASE.nlambda, BASE.mr, BASE.nbits_r, BASE.k, BASE.nq
+
+
+def world(geo=BASE):
+    return geo.world()
+
+
+def near(rng, cells, geo=BASE):
     """one row beside the coarse centroid of each given cell"""
-    return (_world["coarse"][np.asarray(cells)] + 0.3 * rng.randn(len(cells), D_)).astype(np.float32)
+    return (geo._world["coarse"][np.asarray(cells)] + 0.3 * rng.randn(len(cells), geo.d)).astype(np.float32)
 
 
-def make(kind):
-    w = world()
+def make(kind, geo=BASE):
+    w = world(geo)
     if kind == "ivfflat":
-        g = vlq.GpuIVFFlat(D_, NLIST)
+        g = vlq.GpuIVFFlat(geo.d, geo.nlist)
     elif kind == "ivfsq":
-        g = vlq.GpuIVFSQ(D_, NLIST, "8bit")
+        g = vlq.GpuIVFSQ(geo.d, geo.nlist, geo.qtype)
     elif kind == "vlq":
-        g = vlq.GpuVLQ(D_, NLIST, M_, 8, NEDGE, NLAMBDA)
+        g = vlq.GpuVLQ(geo.d, geo.nlist, geo.M, 8, geo.nedge, geo.nlambda)
     else:
-        g = vlq.GpuIVFPQ(D_, NLIST, M_, 8)
+        g = vlq.GpuIVFPQ(geo.d, geo.nlist, geo.M, 8)
     g.set_coarse_centroids(w["coarse"])
     if kind == "ivfsq":
         if "sq_trained" not in w:
@@ -55,23 +73,25 @@ def make(kind):
     if kind in ("ivfpq", "ivfpqr", "vlq"):
         g.set_pq_centroids(w["pq"])
     if kind == "ivfpqr":
-        g.set_refine_pq(MR, NBITS_R, w["rpq"])
+        g.set_refine_pq(geo.mr, geo.nbits_r, w["rpq"])
     if kind == "vlq":
         g.build_graph()
         g.set_lambda_codebook(w["lambda"])
     return g
 
 
-def shape_of(kind):
+def shape_of(kind, geo=BASE):
     """(number of lists, row dtype, row width, side bytes per row)"""
     if kind == "ivfflat":
-        return NLIST, np.float32, D_, 0
+        return geo.nlist, np.float32, geo.d, 0
     if kind == "vlq":
-        return NLIST * NEDGE, np.uint8, M_, 1
-    return NLIST, np.uint8, D_ if kind == "ivfsq" else M_, MR if kind == "ivfpqr" else 0
+        return geo.nlist * geo.nedge, np.uint8, geo.M, 1
+    if kind == "ivfsq":
+        return geo.nlist, np.uint8, geo.d if geo.qtype.startswith("8bit") else (geo.d + 1) // 2, 0
+    return geo.nlist, np.uint8, geo.M, geo.mr if kind == "ivfpqr" else 0
 
 
-def stored_as(kind, g, x):
+def stored_as(kind, g, x, geo=BASE):
     """(list of every row or -1, the rows as stored, their side bytes [n][side]) for the rows x"""
     n = len(x)
     side = np.zeros((n, 0), np.uint8)
@@ -86,19 +106,20 @@ def stored_as(kind, g, x):
         return line.astype(np.int64), codes, lam.reshape(n, 1)
     assign, codes = g.encode(x)
     if kind == "ivfpqr":        # ids of an empty index's first add are the row numbers
-        s = make(kind)
+        s = make(kind, geo)
         s.add(x)
-        side = np.zeros((n, MR), np.uint8)
-        for i in range(NLIST):
+        side = np.zeros((n, geo.mr), np.uint8)
+        for i in np.unique(assign[assign >= 0]):
             side[s.get_list(i)[1]] = s.get_list_refine_codes(i)
     return assign, codes, side
 
 
 class Model:
-    def __init__(self, kind):
-        self.kind = kind
-        self.nlists, self.dtype, self.width, self.side = shape_of(kind)
+    def __init__(self, kind, geo=BASE):
+        self.kind, self.geo = kind, geo
+        self.nlists, self.dtype, self.width, self.side = shape_of(kind, geo)
         self.row_bytes = self.width * np.dtype(self.dtype).itemsize + 8 + self.side
+        self.side_values = geo.nlambda if kind == "vlq" else 1 << geo.nbits_r      # (a lambda index, a refine code)
         self.grown = 0
         self.reset()
 
@@ -118,7 +139,7 @@ class Model:
         assert len(lens) == self.nlists
         nt = int(sum(lens))
         rows = rng.randn(nt, self.width).astype(np.float32) if self.dtype == np.float32 else rng.randint(0, 256, (nt, self.width)).astype(np.uint8)
-        sides = rng.randint(0, 16, (nt, self.side)).astype(np.uint8)      # (a lambda index < NLAMBDA, a refine code < 2^NBITS_R)
+        sides = rng.randint(0, self.side_values, (nt, self.side)).astype(np.uint8)
         ids = (rng.permutation(nt) * 3 + 1000).astype(np.int64)
         cuts = np.cumsum(lens)[:-1]
         self.rows, self.sides, self.ids = np.split(rows, cuts), np.split(sides, cuts), np.split(ids, cuts)
@@ -178,28 +199,29 @@ class Model:
                 assert np.array_equal(g.get_list_refine_codes(i), self.sides[i]), (step, i, "refine codes")
 
 
-def search(kind, g):
-    xq = world()["xq"]
+def search(kind, g, geo=BASE):
+    xq = world(geo)["xq"]
     if kind == "vlq":
-        return g.search(xq, NLIST, NLIST * NEDGE, K)
+        return g.search(xq, geo.nlist, geo.nlist * geo.nedge, geo.k)
     if kind == "ivfpqr":
-        return g.search_refined(xq, NLIST, K, 2.0)
-    return g.search(xq, NLIST, K)
+        return g.search_refined(xq, geo.nlist, geo.k, 2.0)
+    return g.search(xq, geo.nlist, geo.k)
 
 
 def check_search(kind, g, model, step):
     """the rows of g == the rows of a fresh index that got the model through set_lists, bit for bit"""
-    fresh = make(kind)
+    geo = model.geo
+    fresh = make(kind, geo)
     model.load_into(fresh)
-    D, I = search(kind, g)
-    Df, If = search(kind, fresh)
-    assert (If[:, K - 1] >= 0).all(), (step, "every query has K results")
+    D, I = search(kind, g, geo)
+    Df, If = search(kind, fresh, geo)
+    assert (If[:, geo.k - 1] >= 0).all(), (step, "every query has K results")
     assert np.array_equal(D.view(np.uint32), Df.view(np.uint32)), (step, D, Df)
     assert np.array_equal(I, If), (step, I, If)
 
 
 def add(kind, g, model, x):
-    assign, rows, sides = stored_as(kind, g, x)
+    assign, rows, sides = stored_as(kind, g, x, model.geo)
     g.add(x)
     model.add(assign, rows, sides)
 
