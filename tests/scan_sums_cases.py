@@ -66,8 +66,8 @@ def oracle_from(g, coarse, pq, max_codes=0):
                        list_offsets=np.array(off, np.int64), max_codes=max_codes)
 
 
-def common(seed=7):
-    import vector_line_quantization_amd as vlq
+def common_world(seed=7):
+    """the host side of common(): the trained oracle index with its lists, the queries and the generator's state"""
     rng = np.random.default_rng(seed)
     centres = rng.random((200, D_))
     sub = rng.standard_normal((12, D_)) / 12 ** 0.5
@@ -81,11 +81,17 @@ def common(seed=7):
     ox.add(xb, canonical=True)
     lens = np.diff(ox.list_offsets)
     assert lens[empty] == 0 and lens.max() > 1000 and 24 <= lens.mean() < 1024, (lens[empty], lens.max(), lens.mean())
+    xq = gmm(rng, centres, sub, 3072)
+    return rng, ox, coarse, pq, xq, (centres, sub)
+
+
+def common(seed=7):
+    import vector_line_quantization_amd as vlq
+    rng, ox, coarse, pq, xq, (centres, sub) = common_world(seed)
     g = vlq.GpuIVFPQ(D_, NLIST, M_, 8)
     g.set_coarse_centroids(coarse)
     g.set_pq_centroids(pq)
     g.set_lists(ox.codes, ox.ids, ox.list_offsets)
-    xq = gmm(rng, centres, sub, 3072)
     return rng, g, ox, coarse, pq, xq, (centres, sub)
 
 

@@ -10,7 +10,8 @@ import vector_line_quantization_amd as vlq
 pytestmark = pytest.mark.gpu
 
 D_, M_, NBITS, NLIST, NB, NQ, NPROBE, K = 32, 8, 8, 16, 2000, 64, 4, 10
-KINDS = ("l2", "ip", "polysemous", "ivfpqr", "imi", "line", "ivfflat", "ivfsq")
+KINDS = ("l2", "ip", "polysemous", "ivfpqr", "imi", "line", "ivfflat", "ivfsq", "pq", "flat", "sq", "lsh")
+ONE_LIST = ("pq", "flat", "sq", "lsh")          # the handles without inverted lists: add(x), search(x, k)
 
 
 def world():
@@ -39,13 +40,24 @@ def one_cycle(kind, w):
         g = vlq.GpuIVFSQ(D_, NLIST, "8bit")
         g.set_coarse_centroids(w["coarse"])
         g.train(w["xb"])
+    elif kind == "pq":
+        g = vlq.GpuPQ(D_, M_, NBITS)
+        g.set_centroids(w["pq"])
+    elif kind == "flat":
+        g = vlq.GpuFlat(D_)
+    elif kind == "sq":
+        g = vlq.GpuSQ(D_, "8bit")
+        g.train(w["xb"])
+    elif kind == "lsh":
+        g = vlq.GpuLSH(D_, 64, rotate_data=True, train_thresholds=True)
+        g.train(w["xb"])
     else:
         g = vlq.GpuIVFPQ(D_, NLIST, M_, NBITS, metric="ip" if kind == "ip" else "l2")
         if kind == "imi":
             g.set_imi_centroids(2, w["imi"])
         else:
             g.set_coarse_centroids(w["coarse"])
-    if kind not in ("ivfflat", "ivfsq"):
+    if kind not in ("ivfflat", "ivfsq") + ONE_LIST:
         g.set_pq_centroids(w["pq"])
     if kind == "polysemous":
         g.set_polysemous_ht(28)
@@ -61,6 +73,8 @@ def one_cycle(kind, w):
         D, I = g.search(xq, NPROBE, 8, K)
     elif kind == "ivfpqr":
         D, I = g.search_refined(xq, NPROBE, K, 2.0)
+    elif kind in ONE_LIST:
+        D, I = g.search(xq, K)
     else:
         D, I = g.search(xq, NPROBE, K)
     assert D.is_cuda and I.is_cuda

@@ -254,6 +254,23 @@ def test_refine_over_flat_and_pq_bases():
     bD, bI = r.base.search(xq, 15)
     Dw, Iw = rr.refine(xb, xq, bD, bI, 5, "l2")
     assert rr.same_bits(D, Dw) and np.array_equal(I, Iw)
+    # ... and over a GpuPQ: a shortlist of approximate distances, re-ranked by the exact ones
+    base = vlq.GpuPQ(16, 4, 8)
+    base.set_centroids((0.6 * rng.standard_normal((4, 256, 4))).astype(np.float32))
+    r = vlq.GpuRefineFlat(base)
+    r.k_factor = 3.0
+    r.add(xb[:300])
+    r.add(xb[300:])
+    assert r.ntotal == 500 == base.ntotal
+    D, I = r.search(xq, 5)
+    bD, bI = base.search(xq, 15)
+    assert not np.array_equal(bI[:, :5], I), "the PQ order is not the exact order: the re-ranking shows"
+    Dw, Iw = rr.refine(xb, xq, bD, bI, 5, "l2")
+    assert rr.same_bits(D, Dw) and np.array_equal(I, Iw)
+    exact = vlq.GpuFlat(16)
+    exact.add(xb)
+    De, Ie = exact.search(xq, 5)
+    assert (I[:, 0] == Ie[:, 0]).mean() >= 0.5, "the best of 15 PQ candidates is the true neighbour for most queries"
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
