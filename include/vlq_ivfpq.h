@@ -97,7 +97,8 @@ int vlq_ivfpq_set_lists(vlq_ivfpq_t h, const uint8_t* codes, const int64_t* ids,
 
 /* IndexIVFPQ::add_with_ids (IndexIVFPQ.cpp:186-272) on the device: coarse 1-NN,
  * residual, per-sub-quantizer argmin (first minimum wins), append in input order.
- * xids may be NULL (ids ntotal..ntotal+n-1).  x [h|d], xids [h|d]. */
+ * xids may be NULL (ids ntotal..ntotal+n-1).  x [h|d], xids [h|d].  Synchronises the stream (the append reads its
+ * totals on the host): the vectors are stored on return. */
 int vlq_ivfpq_add(vlq_ivfpq_t h, int64_t n, const float* x, const int64_t* xids);
 
 /* GpuIndexIVFPQ::reserveMemory (gpu/GpuIndexIVFPQ.cu:283-290 -> IVFBase::reserveMemory,
@@ -328,7 +329,8 @@ int vlq_merge_topk(int device, void* hip_stream, int64_t nq, int k, int nparts, 
 int vlq_ivfpq_query_tables(vlq_ivfpq_t h, int64_t n, const float* x, int inner_product, float* out);
 int vlq_ivfpq_get_precomputed_table(vlq_ivfpq_t h, float* out);
 
-/* indexIVFPQ_stats (IndexIVFPQ.h:169-195): codes visited since the last reset. */
+/* indexIVFPQ_stats (IndexIVFPQ.h:169-195): codes visited since the last reset.  Synchronises the stream; raises a
+ * pending bad-key (or bad-pair) error, once.  The reset is issued on the stream, behind everything issued before it. */
 int vlq_ivfpq_stats(vlq_ivfpq_t h, uint64_t* nq, uint64_t* ncode, int reset);
 
 /* Introspection, speed only (replaces nothing in the reference): what the last search's list scan was -- the kernel shape
@@ -384,7 +386,7 @@ int vlq_ivfflat_set_coarse_centroids(vlq_ivfflat_t h, const float* centroids);
  * list_offsets[nlist+1] [h|d].  Replaces the lists. */
 int vlq_ivfflat_set_lists(vlq_ivfflat_t h, const float* vecs, const int64_t* ids, const int64_t* list_offsets);
 /* IndexIVFFlat::add_with_ids (IndexIVF.cpp:216-219): quantizer->assign (1-NN), then add_core; assigned and appended on the
- * device.  x[n*d] [h|d], xids[n] [h|d] or NULL. */
+ * device.  x[n*d] [h|d], xids[n] [h|d] or NULL.  Synchronises the stream: the vectors are stored on return. */
 int vlq_ivfflat_add(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* xids);
 /* IndexIVFFlat::add_core with precomputed_idx (IndexIVF.cpp:221-262): vector i goes to the end of list assign[i]; a negative
  * list id drops it (:243-244); vectors of one list keep their input order; the id of vector i is xids ? xids[i] :
@@ -409,9 +411,11 @@ int vlq_ivfflat_search_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, c
                                    float* D, int64_t* I);
 /* IndexIVFFlat::range_search (IndexIVF.cpp:401-449).  lims[n+1] [h|d]; *total = lims[n] (host, may be NULL).
  * The hits stay in the handle until the next range search, reset or destroy.  Every range search call drops the previous hits
- * before it looks at its arguments: after a call that failed, for whatever reason, the handle holds an empty result. */
+ * before it looks at its arguments: after a call that failed, for whatever reason, the handle holds an empty result.
+ * Synchronises the stream once (the number of hits is read on the host): lims is complete on return. */
 int vlq_ivfflat_range_search(vlq_ivfflat_t h, int64_t n, const float* x, int nprobe, float radius, int64_t* lims, int64_t* total);
-/* the same from the caller's probes: keys[n*nprobe] [h|d]; a key < 0 or >= nlist: VLQ_ERR_INVALID (the reference aborts) */
+/* the same from the caller's probes: keys[n*nprobe] [h|d]; a key < 0 or >= nlist: VLQ_ERR_INVALID (the reference aborts).
+ * Synchronises the stream once, like vlq_ivfflat_range_search. */
 int vlq_ivfflat_range_search_preassigned(vlq_ivfflat_t h, int64_t n, const float* x, const int64_t* keys, int nprobe, float radius,
                                          int64_t* lims, int64_t* total);
 /* RangeSearchResult::distances / labels of the last range search: D[total], I[total] [h|d], either may be NULL; may be called
@@ -469,11 +473,13 @@ int vlq_ivfsq_code_size(vlq_ivfsq_t h);
 int vlq_ivfsq_set_lists(vlq_ivfsq_t h, const uint8_t* codes, const int64_t* ids, const int64_t* list_offsets);
 /* IndexIVFScalarQuantizer::add_with_ids (:842-881): quantizer->assign (1-NN), residual, encode_vector (:446-455, :520-529:
  * (r_i - vmin_i) / vdiff_i clamped to [0, 1]; (int)(255 * xi) in float at 8 bits, (int)(xi * 15.0) in double at 4 bits), append
- * in input order; the id of vector i is xids ? xids[i] : ntotal + i.  x[n*d], xids[n] [h|d] or NULL. */
+ * in input order; the id of vector i is xids ? xids[i] : ntotal + i.  x[n*d], xids[n] [h|d] or NULL.  Synchronises the
+ * stream: the vectors are stored on return. */
 int vlq_ivfsq_add(vlq_ivfsq_t h, int64_t n, const float* x, const int64_t* xids);
 /* the same with a given assignment instead of quantizer->assign: a list id < 0 or >= nlist drops the vector (:862) */
 int vlq_ivfsq_add_preassigned(vlq_ivfsq_t h, int64_t n, const float* x, const int64_t* xids, const int64_t* assign);
-/* the codes add would store, nothing stored: codes[n*code_size] [h|d]; assign_out[n] [h|d] or NULL */
+/* the codes add would store, nothing stored: codes[n*code_size] [h|d]; assign_out[n] [h|d] or NULL.  Synchronises the stream,
+ * for device outputs too. */
 int vlq_ivfsq_encode(vlq_ivfsq_t h, int64_t n, const float* x, uint8_t* codes, int64_t* assign_out);
 int vlq_ivfsq_reserve_memory(vlq_ivfsq_t h, int64_t num_vecs);
 int vlq_ivfsq_reclaim_memory(vlq_ivfsq_t h, uint64_t* bytes_reclaimed);
@@ -534,9 +540,11 @@ int vlq_pq_set_stream(vlq_pq_t h, void* hip_stream);
 int vlq_pq_set_centroids(vlq_pq_t h, const float* centroids);
 /* IndexPQ::codes (index_io.cpp:587): codes[n*M] [h|d]; replaces the stored codes */
 int vlq_pq_set_codes(vlq_pq_t h, const uint8_t* codes, int64_t n);
-/* IndexPQ::add (IndexPQ.cpp:78-84): pq.compute_codes on the device, the first minimum per sub-quantizer.  x[n*d] [h|d] */
+/* IndexPQ::add (IndexPQ.cpp:78-84): pq.compute_codes on the device, the first minimum per sub-quantizer.  x[n*d] [h|d].
+ * Synchronises the stream: the codes are stored on return. */
 int vlq_pq_add(vlq_pq_t h, int64_t n, const float* x);
-/* pq.compute_codes (ProductQuantizer.cpp:385-407), nothing stored: codes_out[n*M] [h|d] */
+/* pq.compute_codes (ProductQuantizer.cpp:385-407), nothing stored: codes_out[n*M] [h|d].  Synchronises the stream, for a
+ * device codes_out too. */
 int vlq_pq_encode(vlq_pq_t h, int64_t n, const float* x, uint8_t* codes_out);
 /* codes i0 .. i0+ni-1 in scan order (what IndexPQ::reconstruct_n decodes, IndexPQ.cpp:94-101): out[ni*M] [h|d] */
 int vlq_pq_get_codes(vlq_pq_t h, int64_t i0, int64_t ni, uint8_t* out);
@@ -601,9 +609,11 @@ int vlq_sq_get_trained(vlq_sq_t h, float* out, int count);
 int vlq_sq_code_size(vlq_sq_t h);
 /* IndexScalarQuantizer::codes (index_io.cpp:608): codes[n*code_size] [h|d]; replaces the stored codes */
 int vlq_sq_set_codes(vlq_sq_t h, const uint8_t* codes, int64_t n);
-/* IndexScalarQuantizer::add (:719-725): sq.compute_codes on the device, appended in input order.  x[n*d] [h|d] */
+/* IndexScalarQuantizer::add (:719-725): sq.compute_codes on the device, appended in input order.  x[n*d] [h|d].
+ * Synchronises the stream: the codes are stored on return. */
 int vlq_sq_add(vlq_sq_t h, int64_t n, const float* x);
-/* sq.compute_codes (:674-683), nothing stored: codes_out[n*code_size] [h|d] */
+/* sq.compute_codes (:674-683), nothing stored: codes_out[n*code_size] [h|d].  Synchronises the stream, for a device
+ * codes_out too. */
 int vlq_sq_encode(vlq_sq_t h, int64_t n, const float* x, uint8_t* codes_out);
 /* codes i0 .. i0+ni-1 in scan order: out[ni*code_size] [h|d] */
 int vlq_sq_get_codes(vlq_sq_t h, int64_t i0, int64_t ni, uint8_t* out);
@@ -652,7 +662,8 @@ typedef struct vlq_flat_s* vlq_flat_t;
 int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric);
 void vlq_flat_destroy(vlq_flat_t h);
 int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream);
-/* IndexFlat::add (IndexFlat.cpp:24-28): x[n*d] [h|d] appended in input order; label of a vector = its position */
+/* IndexFlat::add (IndexFlat.cpp:24-28): x[n*d] [h|d] appended in input order; label of a vector = its position.
+ * Synchronises the stream: the vectors are stored on return. */
 int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x);
 int64_t vlq_flat_ntotal(vlq_flat_t h);
 /* IndexFlat::reset (IndexFlat.cpp:35-38) */
@@ -680,14 +691,15 @@ int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap);
  * IndexFlat.cpp:240-242) and its outputs are undefined; the next call starts clean.  Both calls synchronise the stream once, to
  * read that flag.  Queries go to the device in pages of 32 768, as vlq_flat_search's.  Pointers [h|d], on the handle's stream. */
 /* IndexFlat::compute_distance_subset (IndexFlat.cpp:73-93): distances[n*k] in / out -- entry (i, j) becomes the distance of
- * x[i] to vector labels[i*k + j]; entries whose label is < 0 are left untouched */
+ * x[i] to vector labels[i*k + j]; entries whose label is < 0 are left untouched.  Synchronises the stream once. */
 int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, int k, float* distances, const int64_t* labels);
 /* The seam of IndexRefineFlat::search, lines 245-260 and nothing else: compute_distance_subset over the shortlist
  * base_D / base_I [n*k_base], then reorder_2_heaps (IndexFlat.cpp:194-213) into D / I [n*k].  L2: the k smallest by the total
  * order (distance, shortlist position), ascending; inner product: the k largest, the lower shortlist position first among equals,
  * descending.  A skipped entry takes part with the distance it carries and its label, so the base's FLT_MAX / -FLT_MAX padding
  * lands at the end.  Rows equal the reference's heap result up to the order inside groups of exactly equal distance.  D / I may
- * be base_D / base_I when k == k_base (the reference works in place there); otherwise they must not overlap them. */
+ * be base_D / base_I when k == k_base (the reference works in place there); otherwise they must not overlap them.
+ * Synchronises the stream once: the rows are complete on return. */
 int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const float* base_D, const int64_t* base_I, int k, float* D,
                     int64_t* I);
 /* Introspection: the kernel shape the last of the two calls ran, as text,
@@ -732,9 +744,11 @@ int vlq_lsh_set_thresholds(vlq_lsh_t h, const float* t);
 /* apply_preprocess (IndexLSH.cpp:50-81): xt_out[n*nbits] [h|d].  Thresholds are subtracted once they are set; before that the
  * rows are what IndexLSH::train sorts (:89-92) */
 int vlq_lsh_apply(vlq_lsh_t h, int64_t n, const float* x, float* xt_out);
-/* fvecs2bitvecs(apply_preprocess(x)) (IndexLSH.cpp:119-123): codes_out[n*bytes_per_vec] [h|d], nothing stored */
+/* fvecs2bitvecs(apply_preprocess(x)) (IndexLSH.cpp:119-123): codes_out[n*bytes_per_vec] [h|d], nothing stored.
+ * Synchronises the stream, for a device codes_out too. */
 int vlq_lsh_encode(vlq_lsh_t h, int64_t n, const float* x, uint8_t* codes_out);
-/* IndexLSH::add (IndexLSH.cpp:116-125): appended in input order, label of a vector = its position */
+/* IndexLSH::add (IndexLSH.cpp:116-125): appended in input order, label of a vector = its position.  Synchronises the
+ * stream: the codes are stored on return. */
 int vlq_lsh_add(vlq_lsh_t h, int64_t n, const float* x);
 /* ready-made codes[n*bytes_per_vec] [h|d] appended as they are (IndexLSH::codes, index_io.cpp:549-575 "IxHe") */
 int vlq_lsh_add_codes(vlq_lsh_t h, int64_t n, const uint8_t* codes);

@@ -70,6 +70,7 @@ int vlq_line_get_list(vlq_line_t h, int64_t line, uint8_t* codes_out, uint8_t* l
  * lines_out (optional, host, [n*w1]): the selected line ids in selection order. */
 int vlq_line_search(vlq_line_t h, int64_t n, const float* x, int nprobe, int w1, int k, float* D,
                     int64_t* I, int32_t* lines_out);
+/* codes visited since the last reset.  Synchronises the stream; the reset is issued on the stream. */
 int vlq_line_stats(vlq_line_t h, uint64_t* ncode, int reset);
 /* Scan-kernel time of the searches since the last reset, measured with HIP events recorded on the index's stream
  * around every scan launch (what bench.py prices against the roofline; the role of the reference's KernelTimer,

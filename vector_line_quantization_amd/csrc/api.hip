@@ -100,12 +100,14 @@ int bad_flag_error(int bad) {
 }
 
 // An out-of-range probe key aborts the reference's search (IndexIVFPQ.cpp:1008-1011).  The scan
-// kernels raise a device flag; call this after the stream has been synchronised (host outputs).
+// kernels raise a device flag; call this after a call with host outputs.  The flag is read and cleared on the
+// handle's stream: a clear on the legacy stream is not ordered before the next scan on a non-blocking stream.
 int read_bad_key(vlq_ivfpq_t h) {
     int bad = 0;
-    HIP_TRY(hipMemcpy(&bad, reinterpret_cast<const char*>(h->stats.p) + 8, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpyAsync(&bad, reinterpret_cast<const char*>(h->stats.p) + 8, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     if (!bad) return VLQ_OK;
-    HIP_TRY(hipMemset(reinterpret_cast<char*>(h->stats.p) + 8, 0, 8));
+    HIP_TRY(hipMemsetAsync(reinterpret_cast<char*>(h->stats.p) + 8, 0, 8, h->stream));
     return bad_flag_error(bad);
 }
 
@@ -613,7 +615,8 @@ int vlq_ivfpq_last_scan_info(vlq_ivfpq_t h, char* buf, int cap) {
         order = "list-id walk";
         if (h->last_walk_counts) {      // decided on the device from walk_stat_kernel's counts (the handle's own copy of them)
             int v[32];
-            HIP_TRY(hipMemcpy(v, h->walk_counts.p, sizeof(v), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpyAsync(v, h->walk_counts.p, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
             shared = 0;
             for (int x : v) shared += x;
             if (shared > h->last_walk_limit) order = "coarse-distance order";
@@ -622,7 +625,8 @@ int vlq_ivfpq_last_scan_info(vlq_ivfpq_t h, char* buf, int cap) {
     int period = 0, launch_period = 0;      // XCD 0: the running mean of the measured walk times / what the last launch ran with
     if (h->walk_state.p) {
         int ws[8 * 16];
-        HIP_TRY(hipMemcpy(ws, h->walk_state.p, sizeof(ws), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpyAsync(ws, h->walk_state.p, sizeof(ws), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
         period = ws[0]; launch_period = ws[1];
     }
     snprintf(buf, (size_t)cap, "kernel=%s order=%s first=%d shared=%d/%d limit=%d period_ticks=%d launch_period_ticks=%d placement=%s rows=%s",

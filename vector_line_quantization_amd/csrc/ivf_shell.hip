@@ -31,10 +31,12 @@ int ivf_search_args(const IvfShell* f, bool fits, const char* kind, int64_t n, c
 }
 
 int ivf_bad_key(IvfShell* f, const char* msg) {
-    int bad = 0;
-    HIP_TRY(hipMemcpy(&bad, reinterpret_cast<const char*>(f->stats.p) + 8, sizeof(int), hipMemcpyDeviceToHost));
+    int bad = 0;      // read and cleared on the handle's stream: the legacy stream is not ordered with a non-blocking one
+    hipStream_t s = f->cq->stream;
+    HIP_TRY(hipMemcpyAsync(&bad, reinterpret_cast<const char*>(f->stats.p) + 8, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     if (!bad) return VLQ_OK;
-    HIP_TRY(hipMemset(reinterpret_cast<char*>(f->stats.p) + 8, 0, 8));
+    HIP_TRY(hipMemsetAsync(reinterpret_cast<char*>(f->stats.p) + 8, 0, 8, s));
     return fail(VLQ_ERR_INVALID, "%s", msg);
 }
 

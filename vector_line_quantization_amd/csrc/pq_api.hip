@@ -143,7 +143,8 @@ int vlq_pq_create(vlq_pq_t* out, int device, int d, int M, int nbits, int metric
     if (rc == VLQ_OK) rc = h->ws_qcodes.reserve(16);
     if (rc == VLQ_OK) rc = h->ws_part.reserve(16);
     if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, 1, M, 0, h->st.stream);
-    if (rc == VLQ_OK && hipMemset(h->n_pass.p, 0, 8) != hipSuccess) rc = fail(VLQ_ERR_HIP, "hipMemset failed");
+    if (rc == VLQ_OK && (hipMemsetAsync(h->n_pass.p, 0, 8, h->st.stream) != hipSuccess || hipStreamSynchronize(h->st.stream) != hipSuccess))
+        rc = fail(VLQ_ERR_HIP, "hipMemset failed");
     if (rc != VLQ_OK) { vlq_pq_destroy(h); return rc; }
     *out = h;
     return VLQ_OK;
@@ -324,14 +325,14 @@ int vlq_pq_query_codes(vlq_pq_t h, int64_t n, const float* x, uint8_t* out) {
 int vlq_pq_stats(vlq_pq_t h, uint64_t* nq, uint64_t* ncode, uint64_t* n_hamming_pass, int reset) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     TRY(set_dev(&h->st));
+    unsigned long long np = 0;      // read and cleared on the handle's stream: a legacy-stream clear is not ordered before the next search
+    HIP_TRY(hipMemcpyAsync(&np, h->n_pass.p, 8, hipMemcpyDeviceToHost, h->st.stream));
     HIP_TRY(hipStreamSynchronize(h->st.stream));
-    unsigned long long np = 0;
-    HIP_TRY(hipMemcpy(&np, h->n_pass.p, 8, hipMemcpyDeviceToHost));
     if (nq) *nq = h->stat_nq;
     if (ncode) *ncode = h->stat_ncode;
     if (n_hamming_pass) *n_hamming_pass = np;
     if (reset) {
-        HIP_TRY(hipMemset(h->n_pass.p, 0, 8));
+        HIP_TRY(hipMemsetAsync(h->n_pass.p, 0, 8, h->st.stream));
         h->stat_nq = h->stat_ncode = 0;
     }
     return VLQ_OK;
