@@ -7,13 +7,13 @@
 
 namespace vlq_detail {
 
-int set_dev(vlq_ivfpq_t h) {
+int set_dev(const DevCtx* h) {
     HIP_TRY(hipSetDevice(h->device));
     return VLQ_OK;
 }
 
 // stage an input: returns a device pointer holding `bytes` of src
-int stage_in(vlq_ivfpq_t h, const void* src, size_t bytes, DevBuf& ws, const void** out) {
+int stage_in(const DevCtx* h, const void* src, size_t bytes, DevBuf& ws, const void** out) {
     if (bytes == 0) { *out = src; return VLQ_OK; }
     if (is_device_ptr(src)) { *out = src; return VLQ_OK; }
     TRY(ws.reserve(bytes));
@@ -56,7 +56,7 @@ int check_search_args(vlq_ivfpq_t h, int64_t n, const void* x, int nprobe, int k
     return VLQ_OK;
 }
 
-static int finish_outputs(vlq_ivfpq_t h, bool copyD, void* D, const void* Dd, size_t bytesD, bool copyI,
+static int finish_outputs(const DevCtx* h, bool copyD, void* D, const void* Dd, size_t bytesD, bool copyI,
                    void* I, const void* Id, size_t bytesI) {
     if (copyD) HIP_TRY(hipMemcpyAsync(D, Dd, bytesD, hipMemcpyDeviceToHost, h->stream));
     if (copyI) HIP_TRY(hipMemcpyAsync(I, Id, bytesI, hipMemcpyDeviceToHost, h->stream));
@@ -73,7 +73,7 @@ int StagedRows::stage(void* D_out, size_t bytes_D, DevBuf& ws_D, void* I_out, si
     return VLQ_OK;
 }
 
-int StagedRows::finish(vlq_ivfpq_t h) {
+int StagedRows::finish(const DevCtx* h) {
     TRY(finish_outputs(h, copyD, hostD, D, bytesD, copyI, hostI, I, bytesI));
     if (zero_copy && !synchronous()) HIP_TRY(hipStreamSynchronize(h->stream));    // rows in the caller's memory on return
     return VLQ_OK;

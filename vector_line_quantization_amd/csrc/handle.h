@@ -1,4 +1,7 @@
-// Internal: the index handle and small host helpers shared by the host files (api.hip, the stage files, line_api.hip).
+// Internal: what every host file shares.  The error slot and HIP_TRY / TRY, DevBuf, DevCtx (a handle's device and streams: all
+// that the staging of inputs and outputs -- set_dev, stage_in, StagedRows, api.hip -- reads of a handle), ListStore, and the
+// IVFPQ handle with the entry points of its stages.  The shells over it: ivf_shell.h (IVFFlat, IVFSQ: they own an IVFPQ handle
+// as their coarse quantizer) and one_list.h (PQ, SQ, Flat, LSH: a DevCtx and one list, no IVFPQ handle).
 #pragma once
 #include "../../include/vlq_ivfpq.h"
 #include "dev_buf.h"
@@ -63,6 +66,10 @@ inline int ptr_kind(const void* p, void** dev = nullptr) {
     return 0;
 }
 
+// the device a handle lives on, the private non-blocking stream it was created with, and the stream its work is issued on
+// (own_stream until set_stream hands it the caller's)
+struct DevCtx { int device = 0; hipStream_t own_stream = nullptr, stream = nullptr; };
+
 inline bool is_device_ptr(const void* p) {
     if (!p) return false;
     hipPointerAttribute_t attr;
@@ -93,14 +100,13 @@ struct ListStore {
 };
 }  // namespace vlq
 
-struct vlq_ivfpq_s {
-    int device = 0, d = 0, nlist = 0, M = 0, nbits = 0, ksub = 0, dsub = 0;
+struct vlq_ivfpq_s : vlq_detail::DevCtx {
+    int d = 0, nlist = 0, M = 0, nbits = 0, ksub = 0, dsub = 0;
     int by_residual = 1, use_precomputed_table = 1;
     int metric = 1;               // the reference's MetricType (Index.h): 0 = inner product, 1 = L2 (vlq_ivfpq_set_metric)
     DevBuf czero;                 // [nlist] zeros: the centroid "norms" of the inner-product coarse stage
     int64_t max_codes = 0;
     int64_t ntotal = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
 
     vlq::ListStore lists;         // the inverted lists; IVFPQR: lists.side holds the refine codes (side_size = Mr)
     DevBuf coarse, cnorm, pq, pq_t, rnorm, term2;
@@ -201,8 +207,8 @@ struct vlq_ivfpq_s {
 // internal entry points: what crosses the host files
 namespace vlq_detail {
 // api.hip: staging and the checks the entry points share
-int set_dev(vlq_ivfpq_t h);
-int stage_in(vlq_ivfpq_t h, const void* src, size_t bytes, DevBuf& ws, const void** out);
+int set_dev(const DevCtx* h);
+int stage_in(const DevCtx* h, const void* src, size_t bytes, DevBuf& ws, const void** out);
 // The rows of a call's two outputs (D and I; the coarse stage's distances and keys).  stage() picks where the kernels write each:
 // the caller's device memory, with zero_copy_ok its page-locked host memory, or the workspace; finish() copies workspace rows back
 // and synchronises (rows written straight into page-locked memory: synchronises too).
@@ -211,7 +217,7 @@ struct StagedRows {
     size_t bytesD = 0, bytesI = 0;
     bool copyD = false, copyI = false, zero_copy = false;
     int stage(void* D_out, size_t bytes_D, DevBuf& ws_D, void* I_out, size_t bytes_I, DevBuf& ws_I, bool zero_copy_ok = false);
-    int finish(vlq_ivfpq_t h);
+    int finish(const DevCtx* h);
     bool synchronous() const { return copyD || copyI; }    // host outputs: finish() has synchronised (read_bad_key may follow)
 };
 int check_ready(vlq_ivfpq_t h, bool need_lists);

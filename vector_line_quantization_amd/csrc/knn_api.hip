@@ -1,22 +1,17 @@
 // C ABI of the flat exact k-NN index (include/vlq_ivfpq.h, vlq_flat_*): faiss::IndexFlat / gpu::GpuIndexFlat on the device.
-// Host-side orchestration only: the vectors live in a one-list ListStore as rows of 4 * d bytes (lists.h: growth, reserve and
-// the device-side append come from there, as IVFFlat stores its lists), their squared norms in a buffer that grows with it
-// (launch_row_norms over the appended rows only), the scan is scan_knn.hip under plan_knn (knn_plan.h).
-#include "handle.h"
+// Host-side orchestration only.  The device context, the one list -- the vectors as rows of 4 * d bytes, as IVFFlat stores its
+// lists --, the paged search and the reader of the stored vectors are the one-list shell's (one_list.h); here are what is
+// IndexFlat's own: the squared norms in a buffer that grows with the list (launch_row_norms over the appended rows only), the
+// call's plan and the scan of one page under it (scan_knn.hip, knn_plan.h), and IndexRefineFlat's seam (refine_flat.hip).
 #include "knn_plan.h"
-#include "lists.h"
+#include "one_list.h"
 
-struct vlq_flat_s {
-    vlq_ivfpq_s st;               // the device, the stream and the staging of inputs / outputs (set_dev, stage_in, StagedRows): nothing else of it is used
+struct vlq_flat_s : OneListShell {      // (force_tile: the row tile)
     int d = 0;
     int metric = 1;               // MetricType (Index.h): 0 = inner product, 1 = L2
-    int force_rows = 0, force_s = 0;      // vlq_flat_set_scan_split
-    int64_t ntotal = 0;
-    vlq::ListStore lists;         // one list: the vectors in input order, ids = positions
     DevBuf norms;                 // [capacity] |y|^2 in fvec_norm_L2sqr's order
-    DevBuf ws_x, ws_assign, ws_qn, ws_part, ws_matrix, ws_zero, ws_D, ws_I;
+    DevBuf ws_qn, ws_matrix, ws_zero;
     size_t zero_floats = 0;       // floats of ws_zero known to be zero
-    char last_scan[224] = "";
     // vlq_flat_compute_distance_subset / vlq_flat_refine: the staged labels and base distances, the device flag of a label >= ntotal
     DevBuf ws_rl, ws_rD, refine_bad;
     char last_refine[160] = "";
@@ -29,8 +24,8 @@ int norms_reserve(vlq_flat_t h, int64_t n) {
     if ((size_t)n * 4 <= h->norms.cap) return VLQ_OK;
     DevBuf grown;
     TRY(grown.reserve((size_t)(n + n / 4) * 4));
-    if (h->ntotal > 0) HIP_TRY(hipMemcpyAsync(grown.p, h->norms.p, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));       // the old block is freed below
+    if (h->ntotal > 0) HIP_TRY(hipMemcpyAsync(grown.p, h->norms.p, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->ctx.stream));
+    HIP_TRY(hipStreamSynchronize(h->ctx.stream));       // the old block is freed below
     h->norms = std::move(grown);
     return VLQ_OK;
 }
@@ -51,7 +46,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
     a.nq = n; a.ntotal = h->ntotal; a.d = h->d; a.k = k; a.ip = ip;
     if (P.path == vlq::kKnnGemm && !ip) {
         TRY(h->ws_qn.reserve((size_t)n * 4));
-        vlq::launch_row_norms(xd, n, h->d, h->ws_qn.as<float>(), h->st.stream);
+        vlq::launch_row_norms(xd, n, h->d, h->ws_qn.as<float>(), h->ctx.stream);
         a.qn = h->ws_qn.as<float>();
     }
     if (P.route == vlq::kKnnFused) {
@@ -63,7 +58,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
             const size_t nz = (size_t)std::max<int64_t>(n, P.chunk);
             if (nz > h->zero_floats) {
                 TRY(h->ws_zero.reserve(nz * 4));
-                HIP_TRY(hipMemsetAsync(h->ws_zero.p, 0, nz * 4, h->st.stream));
+                HIP_TRY(hipMemsetAsync(h->ws_zero.p, 0, nz * 4, h->ctx.stream));
                 h->zero_floats = nz;
             }
             a.zeros = h->ws_zero.as<float>();
@@ -71,7 +66,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
     }
     a.part = h->ws_part.as<unsigned long long>();
     a.matrix = h->ws_matrix.as<float>();
-    if (!vlq::launch_knn(a, P, h->st.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat search: no kernel for rows=%d kpl=%d (%s / %s)", P.rows, P.kpl,
+    if (!vlq::launch_knn(a, P, h->ctx.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat search: no kernel for rows=%d kpl=%d (%s / %s)", P.rows, P.kpl,
                                                         vlq::knn_path_name(P.path), vlq::knn_route_name(P.route));
     HIP_TRY(hipGetLastError());
     return VLQ_OK;
@@ -82,7 +77,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
 int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int64_t n, const float* xd, const int64_t* ld, int k_base,
                     const float* bd, int k, float* Dd, int64_t* Id) {
     TRY(h->refine_bad.reserve(16));
-    HIP_TRY(hipMemsetAsync(h->refine_bad.p, 0, 4, h->st.stream));
+    HIP_TRY(hipMemsetAsync(h->refine_bad.p, 0, 4, h->ctx.stream));
     for (int64_t i0 = 0; i0 < n; i0 += P.page) {
         vlq::RefineFlatArgs a = {};
         a.xb = h->lists.codes.as<float>();       // (the one list starts at 0)
@@ -93,7 +88,7 @@ int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int
         a.I = Id ? Id + i0 * k : nullptr;
         a.bad = h->refine_bad.as<int>();
         a.nq = std::min(P.page, n - i0); a.ntotal = h->ntotal; a.d = h->d; a.k_base = k_base; a.k = k; a.ip = h->metric == 0;
-        if (!vlq::launch_refine_flat(a, P, select, h->st.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat refine: no kernel for this plan");
+        if (!vlq::launch_refine_flat(a, P, select, h->ctx.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat refine: no kernel for this plan");
         HIP_TRY(hipGetLastError());
     }
     snprintf(h->last_refine, sizeof(h->last_refine), "kernel=refine_flat_kernel select=%d metric=%s read=%s waves=%d trips=%d slots=%d page=%lld lds=%zu",
@@ -103,8 +98,8 @@ int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int
 
 int refine_flat_bad(vlq_flat_t h) {
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, h->refine_bad.p, 4, hipMemcpyDeviceToHost, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    HIP_TRY(hipMemcpyAsync(&bad, h->refine_bad.p, 4, hipMemcpyDeviceToHost, h->ctx.stream));
+    HIP_TRY(hipStreamSynchronize(h->ctx.stream));
     if (bad) return fail(VLQ_ERR_INVALID, "a label >= ntotal=%lld was passed (IndexFlat.cpp:240-242 asserts); the results of this call are undefined", (long long)h->ntotal);
     return VLQ_OK;
 }
@@ -123,42 +118,19 @@ int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric) {
     if (d <= 0) return fail(VLQ_ERR_INVALID, "d=%d must be positive", d);
     if (d > (1 << 26)) return fail(VLQ_ERR_UNSUPPORTED, "d=%d: rows beyond 2^28 bytes", d);
     if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
-    const int ndev = vlq_device_count();
-    if (ndev <= 0) return fail(VLQ_ERR_HIP, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(VLQ_ERR_INVALID, "device %d out of range", device);
     vlq_flat_s* h = new (std::nothrow) vlq_flat_s();
     if (!h) return fail(VLQ_ERR_INVALID, "out of memory");
-    h->st.device = device;
     h->d = d; h->metric = metric;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st.own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail(VLQ_ERR_HIP, "device init failed: %s", hipGetErrorString(e)); }
-    h->st.stream = h->st.own_stream;
-    int rc = h->ws_part.reserve(16);
+    int rc = one_open(h, device, 4 * d);
     if (rc == VLQ_OK) rc = h->ws_matrix.reserve(16);
     if (rc == VLQ_OK) rc = h->norms.reserve(16);
-    if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, 1, 4 * d, 0, h->st.stream);
     if (rc != VLQ_OK) { vlq_flat_destroy(h); return rc; }
     *out = h;
     return VLQ_OK;
 }
 
-void vlq_flat_destroy(vlq_flat_t h) {
-    if (!h) return;
-    (void)hipSetDevice(h->st.device);
-    (void)hipStreamSynchronize(h->st.stream);
-    const hipStream_t own = h->st.own_stream;
-    delete h;       // every DevBuf frees its block here, before the stream goes
-    if (own) (void)hipStreamDestroy(own);
-}
-
-int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream) {
-    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    h->st.stream = reinterpret_cast<hipStream_t>(hip_stream);
-    return VLQ_OK;
-}
+void vlq_flat_destroy(vlq_flat_t h) { one_destroy(h); }
+int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream) { return one_set_stream(h, hip_stream); }
 
 // IndexFlat::add (IndexFlat.cpp:24-28): appended in input order; only the new rows' norms are computed
 int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x) {
@@ -167,78 +139,55 @@ int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x) {
     if (n == 0) return VLQ_OK;
     if (h->ntotal + n >= (int64_t(1) << 32))
         return fail(VLQ_ERR_UNSUPPORTED, "ntotal=%lld beyond 2^32 - 1, the key's position field", (long long)(h->ntotal + n));
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void* xd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
-    TRY(h->ws_assign.reserve((size_t)n * 8));
-    HIP_TRY(hipMemsetAsync(h->ws_assign.p, 0, (size_t)n * 8, h->st.stream));       // every vector goes to list 0
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(one_route(h, n));
     TRY(norms_reserve(h, h->ntotal + n));
-    int64_t placed = 0;
-    TRY(vlq::lists_append(h->lists, n, h->ws_assign.as<int64_t>(), nullptr, (const uint8_t*)xd, nullptr, nullptr, h->ntotal, h->st.stream,
-                          &placed));
+    const int64_t n0 = h->ntotal;
+    TRY(one_append(h, n, (const uint8_t*)xd));
     // (the one list starts at 0: the new rows sit behind the stored ones)
-    vlq::launch_row_norms(h->lists.codes.as<float>() + (size_t)h->ntotal * h->d, placed, h->d, h->norms.as<float>() + h->ntotal, h->st.stream);
+    vlq::launch_row_norms(h->lists.codes.as<float>() + (size_t)n0 * h->d, h->ntotal - n0, h->d, h->norms.as<float>() + n0, h->ctx.stream);
     HIP_TRY(hipGetLastError());
-    h->ntotal += placed;
     return VLQ_OK;
 }
 
-int64_t vlq_flat_ntotal(vlq_flat_t h) { return h ? h->ntotal : -1; }
-
-// IndexFlat::reset (IndexFlat.cpp:35-38)
-int vlq_flat_reset(vlq_flat_t h) {
-    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    TRY(set_dev(&h->st));
-    TRY(vlq::lists_clear(h->lists, h->st.stream));
-    h->ntotal = 0;
-    return VLQ_OK;
-}
+int64_t vlq_flat_ntotal(vlq_flat_t h) { return one_ntotal(h); }
+int vlq_flat_reset(vlq_flat_t h) { return one_reset(h); }       // IndexFlat::reset (IndexFlat.cpp:35-38)
 
 int vlq_flat_reserve_memory(vlq_flat_t h, int64_t num_vecs) {
     if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument: num_vecs=%lld", (long long)num_vecs);
     if (num_vecs >= (int64_t(1) << 32)) return fail(VLQ_ERR_UNSUPPORTED, "num_vecs=%lld beyond 2^32 - 1, the key's position field", (long long)num_vecs);
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     TRY(norms_reserve(h, num_vecs));
-    return vlq::lists_reserve(h->lists, num_vecs, h->st.stream);
+    return one_reserve(h, num_vecs);
 }
 
 int vlq_flat_reconstruct_n(vlq_flat_t h, int64_t i0, int64_t n, float* out) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (n < 0 || (n > 0 && (i0 < 0 || i0 + n > h->ntotal)))
         return fail(VLQ_ERR_INVALID, "vectors %lld .. %lld outside 0 .. ntotal=%lld", (long long)i0, (long long)(i0 + n), (long long)h->ntotal);
-    if (n == 0) return VLQ_OK;
-    if (!out) return fail(VLQ_ERR_INVALID, "null out");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    HIP_TRY(hipMemcpy(out, h->lists.codes.as<float>() + (size_t)i0 * h->d, (size_t)n * h->d * 4, hipMemcpyDefault));      // (the one list starts at 0)
-    return VLQ_OK;
+    return one_get_rows(h, i0, n, out);
 }
 
 // IndexFlat::search (IndexFlat.cpp:41-56)
 int vlq_flat_search(vlq_flat_t h, int64_t n, const float* x, int k, float* D, int64_t* I) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
-    if (n > 0 && (!x || !D || !I)) return fail(VLQ_ERR_INVALID, "null buffer");
-    if (k < 1) return fail(VLQ_ERR_INVALID, "k=%d must be positive", k);
-    if (k > VLQ_MAX_K) return fail(VLQ_ERR_UNSUPPORTED, "k=%d beyond %d", k, VLQ_MAX_K);
+    TRY(one_search_args(n, x, k, D, I));
     if (n == 0) return VLQ_OK;
     // the dispatch and the plan are the call's: a last short page takes the path of the first (utils.cpp:741, :939)
-    const vlq::KnnPlan P = vlq::plan_knn(n, h->ntotal, h->d, k, h->force_rows, h->force_s);
+    const vlq::KnnPlan P = vlq::plan_knn(n, h->ntotal, h->d, k, h->force_tile, h->force_s);
     if (!P.ok) return flat_plan_fail(h, n, k, P);
-    TRY(set_dev(&h->st));
-    StagedRows out;
-    TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I, true));
-    const void* xd = nullptr;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
-    for (int64_t i0 = 0; i0 < n; i0 += P.page) {
-        const int64_t ni = std::min(P.page, n - i0);
-        TRY(flat_search_page(h, P, ni, (const float*)xd + i0 * h->d, k, (float*)out.D + i0 * k, (int64_t*)out.I + i0 * k));
-    }
-    snprintf(h->last_scan, sizeof(h->last_scan), "path=%s route=%s kernel=%s rows=%d S=%d slice=%lld chunk=%lld page=%lld lds=%zu join=%d",
-             vlq::knn_path_name(P.path), vlq::knn_route_name(P.route),
-             P.route == vlq::kKnnFused ? "knn_gemm_kernel" : P.path == vlq::kKnnDirect ? "knn_direct_kernel" : "coarse_dist+knn_select_kernel",
-             P.rows, P.S, (long long)P.slice_len, (long long)P.chunk, (long long)P.page, P.lds, P.join ? 1 : 0);
-    return out.finish(&h->st);
+    return one_search(
+        h, n, x, (size_t)h->d * 4, k, D, I, P.page,
+        [&](int64_t ni, const void* xd, float* Dd, int64_t* Id) { return flat_search_page(h, P, ni, (const float*)xd, k, Dd, Id); },
+        [&] {
+            snprintf(h->last_scan, sizeof(h->last_scan), "path=%s route=%s kernel=%s rows=%d S=%d slice=%lld chunk=%lld page=%lld lds=%zu join=%d",
+                     vlq::knn_path_name(P.path), vlq::knn_route_name(P.route),
+                     P.route == vlq::kKnnFused ? "knn_gemm_kernel" : P.path == vlq::kKnnDirect ? "knn_direct_kernel" : "coarse_dist+knn_select_kernel",
+                     P.rows, P.S, (long long)P.slice_len, (long long)P.chunk, (long long)P.page, P.lds, P.join ? 1 : 0);
+        });
 }
 
 // speed only: results never depend on it
@@ -246,18 +195,12 @@ int vlq_flat_set_scan_split(vlq_flat_t h, int row_tile, int slices) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (row_tile != 0 && row_tile != 32 && row_tile != 64 && row_tile != 128) return fail(VLQ_ERR_INVALID, "row_tile %d (0, 32, 64 or 128)", row_tile);
     if (slices < 0 || slices > vlq::kKnnMaxSlices) return fail(VLQ_ERR_INVALID, "slices %d outside 0..%d", slices, vlq::kKnnMaxSlices);
-    h->force_rows = row_tile;
+    h->force_tile = row_tile;
     h->force_s = slices;
     return VLQ_OK;
 }
 
-int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap) {
-    if (!h || !buf || cap < 1) return fail(VLQ_ERR_INVALID, "null argument");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    snprintf(buf, (size_t)cap, "%s", h->last_scan[0] ? h->last_scan : "kernel=none");
-    return VLQ_OK;
-}
+int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap) { return one_last_scan_info(h, buf, cap); }
 
 // IndexFlat::compute_distance_subset (IndexFlat.cpp:73-93)
 int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, int k, float* distances, const int64_t* labels) {
@@ -267,13 +210,13 @@ int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, in
     const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k, k, false);
     if (!P.ok) return refine_flat_plan_fail(h, k, k, P);
     if (n == 0) return VLQ_OK;
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void *xd, *ld, *dd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
-    TRY(stage_in(&h->st, labels, (size_t)n * k * 8, h->ws_rl, &ld));
-    TRY(stage_in(&h->st, distances, (size_t)n * k * 4, h->ws_rD, &dd));       // in / out: device rows are updated in place
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, labels, (size_t)n * k * 8, h->ws_rl, &ld));
+    TRY(stage_in(&h->ctx, distances, (size_t)n * k * 4, h->ws_rD, &dd));       // in / out: device rows are updated in place
     TRY(refine_flat_dev(h, P, false, n, (const float*)xd, (const int64_t*)ld, k, nullptr, k, (float*)const_cast<void*>(dd), nullptr));
-    if (dd != (const void*)distances) HIP_TRY(hipMemcpyAsync(distances, dd, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->st.stream));
+    if (dd != (const void*)distances) HIP_TRY(hipMemcpyAsync(distances, dd, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->ctx.stream));
     return refine_flat_bad(h);
 }
 
@@ -288,15 +231,15 @@ int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const f
     if (k != k_base && ((const void*)D == (const void*)base_D || (const void*)I == (const void*)base_I))
         return fail(VLQ_ERR_INVALID, "D / I may be base_D / base_I only when k == k_base");
     if (n == 0) return VLQ_OK;
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void *xd, *ld, *bd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
-    TRY(stage_in(&h->st, base_I, (size_t)n * k_base * 8, h->ws_rl, &ld));
-    TRY(stage_in(&h->st, base_D, (size_t)n * k_base * 4, h->ws_rD, &bd));
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, base_I, (size_t)n * k_base * 8, h->ws_rl, &ld));
+    TRY(stage_in(&h->ctx, base_D, (size_t)n * k_base * 4, h->ws_rD, &bd));
     StagedRows out;
     TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I));
     TRY(refine_flat_dev(h, P, true, n, (const float*)xd, (const int64_t*)ld, k_base, (const float*)bd, k, (float*)out.D, (int64_t*)out.I));
-    TRY(out.finish(&h->st));
+    TRY(out.finish(&h->ctx));
     return refine_flat_bad(h);
 }
 

@@ -1,25 +1,20 @@
-// C ABI of the flat PQ index (include/vlq_ivfpq.h, vlq_pq_*): faiss::IndexPQ on the device.  Host-side orchestration only: the
-// codes live in a one-list ListStore (lists.h: growth, reserve and the device-side append come from there), the tables and
-// the encoder are the IVFPQ ones (launch_pq_tables, launch_residual_encode without a residual), the scan is scan_pq.hip under
-// plan_pq_scan (pq_plan.h).
-#include "handle.h"
-#include "lists.h"
+// C ABI of the flat PQ index (include/vlq_ivfpq.h, vlq_pq_*): faiss::IndexPQ on the device.  Host-side orchestration only.  The
+// device context, the one list of codes, the paged search and the readers of the stored codes are the one-list shell's
+// (one_list.h); here are what is IndexPQ's own: the centroids and the SDC table, the search types and their checks, the query
+// tables and codes, the statistics, and the scan of one page -- the IVFPQ tables and encoder (launch_pq_tables,
+// launch_residual_encode without a residual), scan_pq.hip under plan_pq_scan (pq_plan.h).
+#include "one_list.h"
 #include "pq_plan.h"
 
-struct vlq_pq_s {
-    vlq_ivfpq_s st;               // the device, the stream and the staging of inputs / outputs (set_dev, stage_in, StagedRows): nothing else of it is used
+struct vlq_pq_s : OneListShell {
     int d = 0, M = 0, nbits = 0, ksub = 0, dsub = 0;
     int metric = 1;               // MetricType (Index.h): 0 = inner product, 1 = L2
     int search_type = vlq::kPqST_PQ;
     int polysemous_ht = 0;        // IndexPQ.cpp:47: nbits * M + 1
-    int force_q = 0, force_s = 0; // vlq_pq_set_scan_split
-    int64_t ntotal = 0;
-    vlq::ListStore lists;         // one list: the codes in scan order, ids = positions
     DevBuf pq, sdc, n_pass;       // centroids [M][ksub][dsub], sdc_table [M][ksub][ksub], passers (u64)
-    DevBuf ws_x, ws_qtab, ws_qcodes, ws_part, ws_codes, ws_assign, ws_ids, ws_D, ws_I;
+    DevBuf ws_qtab, ws_qcodes, ws_codes;
     bool have_pq = false, sdc_valid = false;
     uint64_t stat_nq = 0, stat_ncode = 0;
-    char last_scan[192] = "";
 };
 
 namespace {
@@ -42,7 +37,7 @@ int pq_search_type_ok(vlq_pq_t h) {
 int pq_ensure_sdc(vlq_pq_t h) {
     if (h->sdc_valid) return VLQ_OK;
     TRY(h->sdc.reserve((size_t)h->M * h->ksub * h->ksub * 4));
-    vlq::launch_pq_sdc_table(h->pq.as<float>(), h->M, h->ksub, h->dsub, h->sdc.as<float>(), h->st.stream);
+    vlq::launch_pq_sdc_table(h->pq.as<float>(), h->M, h->ksub, h->dsub, h->sdc.as<float>(), h->ctx.stream);
     HIP_TRY(hipGetLastError());
     h->sdc_valid = true;
     return VLQ_OK;
@@ -50,7 +45,7 @@ int pq_ensure_sdc(vlq_pq_t h) {
 
 // pq.compute_codes (ProductQuantizer.cpp:385-407) of n device vectors into `codes`
 int pq_encode_dev(vlq_pq_t h, int64_t n, const float* xd, uint8_t* codes) {
-    vlq::launch_residual_encode(xd, n, h->d, nullptr, nullptr, 0, h->pq.as<float>(), h->M, h->ksub, h->dsub, codes, h->st.stream);
+    vlq::launch_residual_encode(xd, n, h->d, nullptr, nullptr, 0, h->pq.as<float>(), h->M, h->ksub, h->dsub, codes, h->ctx.stream);
     HIP_TRY(hipGetLastError());
     return VLQ_OK;
 }
@@ -63,14 +58,14 @@ int pq_prepare_dev(vlq_pq_t h, int64_t n, const float* xd) {
         TRY(pq_ensure_sdc(h));
         TRY(h->ws_qcodes.reserve((size_t)n * h->M + 16));
         TRY(pq_encode_dev(h, n, xd, h->ws_qcodes.as<uint8_t>()));
-        vlq::launch_pq_sdc_gather(h->sdc.as<float>(), h->ws_qcodes.as<uint8_t>(), n, h->M, h->ksub, h->ws_qtab.as<float>(), h->st.stream);
+        vlq::launch_pq_sdc_gather(h->sdc.as<float>(), h->ws_qcodes.as<uint8_t>(), n, h->M, h->ksub, h->ws_qtab.as<float>(), h->ctx.stream);
     } else {
         // compute_distance_tables / compute_inner_prod_tables (ProductQuantizer.cpp:439-493)
         const bool ip = h->search_type == vlq::kPqST_PQ && h->metric == 0;
-        vlq::launch_pq_tables(xd, n, h->d, h->pq.as<float>(), h->M, h->ksub, h->dsub, nullptr, ip ? 0 : 1, h->ws_qtab.as<float>(), h->st.stream);
+        vlq::launch_pq_tables(xd, n, h->d, h->pq.as<float>(), h->M, h->ksub, h->dsub, nullptr, ip ? 0 : 1, h->ws_qtab.as<float>(), h->ctx.stream);
         if (vlq::pq_search_type_filters(h->search_type)) {
             TRY(h->ws_qcodes.reserve((size_t)n * h->M + 16));
-            vlq::launch_pq_table_argmin(h->ws_qtab.as<float>(), n, h->M, h->ksub, h->ws_qcodes.as<uint8_t>(), h->st.stream);
+            vlq::launch_pq_table_argmin(h->ws_qtab.as<float>(), n, h->M, h->ksub, h->ws_qcodes.as<uint8_t>(), h->ctx.stream);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -84,7 +79,7 @@ int pq_plan_fail(vlq_pq_t h, int k, const vlq::PqPlan& P) {
 
 // IndexPQ::search of one page of device queries
 int pq_search_page(vlq_pq_t h, int64_t n, const float* xd, int k, float* Dd, int64_t* Id) {
-    const vlq::PqPlan P = vlq::plan_pq_scan(n, h->ntotal, h->M, h->ksub, k, h->search_type, h->force_q, h->force_s);
+    const vlq::PqPlan P = vlq::plan_pq_scan(n, h->ntotal, h->M, h->ksub, k, h->search_type, h->force_tile, h->force_s);
     if (!P.ok) return pq_plan_fail(h, k, P);
     TRY(pq_prepare_dev(h, n, xd));
     if (P.join) TRY(h->ws_part.reserve((size_t)n * P.S * k * 8));
@@ -98,7 +93,7 @@ int pq_search_page(vlq_pq_t h, int64_t n, const float* xd, int k, float* Dd, int
     a.nq = n; a.ntotal = h->ntotal; a.slice_len = P.slice_len;
     a.M = h->M; a.ksub = h->ksub; a.k = k; a.S = P.S; a.ht = h->polysemous_ht;
     a.neg = (h->search_type == vlq::kPqST_PQ && h->metric == 0) ? 0x80000000u : 0u;
-    if (!vlq::launch_scan_pq(a, P, h->st.stream)) return pq_plan_fail(h, k, P);
+    if (!vlq::launch_scan_pq(a, P, h->ctx.stream)) return pq_plan_fail(h, k, P);
     HIP_TRY(hipGetLastError());
     static const char* const kOrder[] = {"M4", "group4", "left"};
     static const char* const kFilter[] = {"none", "hamming", "generalized"};
@@ -126,52 +121,29 @@ int vlq_pq_create(vlq_pq_t* out, int device, int d, int M, int nbits, int metric
     if (nbits > 8) return fail(VLQ_ERR_UNSUPPORTED, "nbits=%d: two bytes per index are not built (1..8 only)", nbits);
     if (M > vlq::kPqMaxM) return fail(VLQ_ERR_UNSUPPORTED, "M=%d beyond %d", M, vlq::kPqMaxM);
     if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
-    const int ndev = vlq_device_count();
-    if (ndev <= 0) return fail(VLQ_ERR_HIP, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(VLQ_ERR_INVALID, "device %d out of range", device);
     vlq_pq_s* h = new (std::nothrow) vlq_pq_s();
     if (!h) return fail(VLQ_ERR_INVALID, "out of memory");
-    h->st.device = device;
     h->d = d; h->M = M; h->nbits = nbits; h->ksub = 1 << nbits; h->dsub = d / M; h->metric = metric;
     h->polysemous_ht = nbits * M + 1;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st.own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail(VLQ_ERR_HIP, "device init failed: %s", hipGetErrorString(e)); }
-    h->st.stream = h->st.own_stream;
-    int rc = h->pq.reserve((size_t)M * h->ksub * h->dsub * 4);
+    int rc = one_open(h, device, M);
+    if (rc == VLQ_OK) rc = h->pq.reserve((size_t)M * h->ksub * h->dsub * 4);
     if (rc == VLQ_OK) rc = h->n_pass.reserve(8);
     if (rc == VLQ_OK) rc = h->ws_qcodes.reserve(16);
-    if (rc == VLQ_OK) rc = h->ws_part.reserve(16);
-    if (rc == VLQ_OK) rc = vlq::lists_init(h->lists, 1, M, 0, h->st.stream);
-    if (rc == VLQ_OK && (hipMemsetAsync(h->n_pass.p, 0, 8, h->st.stream) != hipSuccess || hipStreamSynchronize(h->st.stream) != hipSuccess))
+    if (rc == VLQ_OK && (hipMemsetAsync(h->n_pass.p, 0, 8, h->ctx.stream) != hipSuccess || hipStreamSynchronize(h->ctx.stream) != hipSuccess))
         rc = fail(VLQ_ERR_HIP, "hipMemset failed");
     if (rc != VLQ_OK) { vlq_pq_destroy(h); return rc; }
     *out = h;
     return VLQ_OK;
 }
 
-void vlq_pq_destroy(vlq_pq_t h) {
-    if (!h) return;
-    (void)hipSetDevice(h->st.device);
-    (void)hipStreamSynchronize(h->st.stream);
-    const hipStream_t own = h->st.own_stream;
-    delete h;       // every DevBuf frees its block here, before the stream goes
-    if (own) (void)hipStreamDestroy(own);
-}
-
-int vlq_pq_set_stream(vlq_pq_t h, void* hip_stream) {
-    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    h->st.stream = reinterpret_cast<hipStream_t>(hip_stream);
-    return VLQ_OK;
-}
+void vlq_pq_destroy(vlq_pq_t h) { one_destroy(h); }
+int vlq_pq_set_stream(vlq_pq_t h, void* hip_stream) { return one_set_stream(h, hip_stream); }
 
 // ProductQuantizer::centroids as pq.train left them (ProductQuantizer.h:37): [M][ksub][dsub]
 int vlq_pq_set_centroids(vlq_pq_t h, const float* centroids) {
     if (!h || !centroids) return fail(VLQ_ERR_INVALID, "null argument");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    TRY(set_dev(&h->ctx));
+    HIP_TRY(hipStreamSynchronize(h->ctx.stream));
     HIP_TRY(hipMemcpy(h->pq.p, centroids, (size_t)h->M * h->ksub * h->dsub * 4, hipMemcpyDefault));
     h->have_pq = true;
     h->sdc_valid = false;
@@ -179,19 +151,7 @@ int vlq_pq_set_centroids(vlq_pq_t h, const float* centroids) {
 }
 
 // IndexPQ::codes as index_io.cpp:587 reads them: [n][M], replaces the stored codes
-int vlq_pq_set_codes(vlq_pq_t h, const uint8_t* codes, int64_t n) {
-    if (!h || n < 0 || (n > 0 && !codes)) return fail(VLQ_ERR_INVALID, "bad argument");
-    if (n >= (int64_t(1) << 32)) return fail(VLQ_ERR_UNSUPPORTED, "ntotal=%lld beyond 2^32 - 1, the key's position field", (long long)n);
-    TRY(set_dev(&h->st));
-    TRY(h->ws_ids.reserve((size_t)n * 8 + 16));
-    vlq::launch_iota(h->ws_ids.as<int64_t>(), n, 0, h->st.stream);
-    HIP_TRY(hipGetLastError());
-    const int64_t off[2] = {0, n};
-    int64_t nt = 0;
-    TRY(vlq::lists_load(h->lists, codes, nullptr, h->ws_ids.as<int64_t>(), off, "codes", vlq::kNoLenLimit, h->st.stream, &nt));
-    h->ntotal = nt;
-    return VLQ_OK;
-}
+int vlq_pq_set_codes(vlq_pq_t h, const uint8_t* codes, int64_t n) { return one_load(h, codes, n); }
 
 // IndexPQ::add (IndexPQ.cpp:78-84): pq.compute_codes, the first minimum per sub-quantizer, appended in input order
 int vlq_pq_add(vlq_pq_t h, int64_t n, const float* x) {
@@ -199,60 +159,39 @@ int vlq_pq_add(vlq_pq_t h, int64_t n, const float* x) {
     if (n < 0 || (n > 0 && !x)) return fail(VLQ_ERR_INVALID, "bad argument");
     if (n == 0) return VLQ_OK;
     if (h->ntotal + n >= (int64_t(1) << 32)) return fail(VLQ_ERR_UNSUPPORTED, "ntotal beyond 2^32 - 1, the key's position field");
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void* xd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
     TRY(h->ws_codes.reserve((size_t)n * h->M + 16));
-    TRY(h->ws_assign.reserve((size_t)n * 8));
-    HIP_TRY(hipMemsetAsync(h->ws_assign.p, 0, (size_t)n * 8, h->st.stream));       // every vector goes to list 0
+    TRY(one_route(h, n));
     TRY(pq_encode_dev(h, n, (const float*)xd, h->ws_codes.as<uint8_t>()));
-    int64_t placed = 0;
-    TRY(vlq::lists_append(h->lists, n, h->ws_assign.as<int64_t>(), nullptr, h->ws_codes.as<uint8_t>(), nullptr, nullptr, h->ntotal,
-                          h->st.stream, &placed));
-    h->ntotal += placed;
-    return VLQ_OK;
+    return one_append(h, n, h->ws_codes.as<uint8_t>());
 }
 
 // pq.compute_codes (ProductQuantizer.cpp:385-407): the codes add would store, nothing stored
 int vlq_pq_encode(vlq_pq_t h, int64_t n, const float* x, uint8_t* codes_out) {
     TRY(pq_check_queries(h, n, x, codes_out));
     if (n == 0) return VLQ_OK;
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void* xd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
     TRY(h->ws_codes.reserve((size_t)n * h->M + 16));
     TRY(pq_encode_dev(h, n, (const float*)xd, h->ws_codes.as<uint8_t>()));
-    HIP_TRY(hipMemcpyAsync(codes_out, h->ws_codes.p, (size_t)n * h->M, hipMemcpyDefault, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    return VLQ_OK;
+    return one_fetch(&h->ctx, codes_out, h->ws_codes.p, (size_t)n * h->M);
 }
 
 int vlq_pq_get_codes(vlq_pq_t h, int64_t i0, int64_t ni, uint8_t* out) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (ni < 0 || (ni > 0 && (i0 < 0 || i0 + ni > h->ntotal))) return fail(VLQ_ERR_INVALID, "codes %lld .. %lld outside 0 .. ntotal", (long long)i0, (long long)(i0 + ni));
-    if (ni == 0) return VLQ_OK;
-    if (!out) return fail(VLQ_ERR_INVALID, "null out");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    HIP_TRY(hipMemcpy(out, h->lists.codes.as<uint8_t>() + (size_t)i0 * h->M, (size_t)ni * h->M, hipMemcpyDefault));      // (the one list starts at 0)
-    return VLQ_OK;
+    return one_get_rows(h, i0, ni, out);
 }
 
-int64_t vlq_pq_ntotal(vlq_pq_t h) { return h ? h->ntotal : -1; }
-
-// IndexPQ::reset (IndexPQ.cpp:88-92)
-int vlq_pq_reset(vlq_pq_t h) {
-    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    TRY(set_dev(&h->st));
-    TRY(vlq::lists_clear(h->lists, h->st.stream));
-    h->ntotal = 0;
-    return VLQ_OK;
-}
+int64_t vlq_pq_ntotal(vlq_pq_t h) { return one_ntotal(h); }
+int vlq_pq_reset(vlq_pq_t h) { return one_reset(h); }       // IndexPQ::reset (IndexPQ.cpp:88-92)
 
 int vlq_pq_reserve_memory(vlq_pq_t h, int64_t num_vecs) {
     if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument");
-    TRY(set_dev(&h->st));
-    return vlq::lists_reserve(h->lists, num_vecs, h->st.stream);
+    return one_reserve(h, num_vecs);
 }
 
 // IndexPQ::search_type / polysemous_ht (IndexPQ.h:75-91), the reference's enum values
@@ -269,27 +208,19 @@ int vlq_pq_set_search_type(vlq_pq_t h, int search_type, int polysemous_ht) {
 // IndexPQ::search (IndexPQ.cpp:124-203)
 int vlq_pq_search(vlq_pq_t h, int64_t n, const float* x, int k, float* D, int64_t* I) {
     TRY(pq_ready(h));
-    if (n < 0) return fail(VLQ_ERR_INVALID, "n < 0");
-    if (n > 0 && (!x || !D || !I)) return fail(VLQ_ERR_INVALID, "null buffer");
-    if (k < 1) return fail(VLQ_ERR_INVALID, "k=%d must be positive", k);
-    if (k > VLQ_MAX_K) return fail(VLQ_ERR_UNSUPPORTED, "k=%d beyond %d", k, VLQ_MAX_K);
+    TRY(one_search_args(n, x, k, D, I));
     TRY(pq_search_type_ok(h));
     if (n == 0) return VLQ_OK;
-    const vlq::PqPlan P0 = vlq::plan_pq_scan(n, h->ntotal, h->M, h->ksub, k, h->search_type, h->force_q, h->force_s);
+    const vlq::PqPlan P0 = vlq::plan_pq_scan(n, h->ntotal, h->M, h->ksub, k, h->search_type, h->force_tile, h->force_s);
     if (!P0.ok) return pq_plan_fail(h, k, P0);
-    TRY(set_dev(&h->st));
-    StagedRows out;
-    TRY(out.stage(D, (size_t)n * k * 4, h->ws_D, I, (size_t)n * k * 8, h->ws_I, true));
-    const void* xd = nullptr;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
     // pages of queries: the tables and the partial rows of a page are bounded (pq_plan.h: kPqQueryPage, kPqScratchLimit)
-    for (int64_t i0 = 0; i0 < n; i0 += P0.page) {
-        const int64_t ni = std::min(P0.page, n - i0);
-        TRY(pq_search_page(h, ni, (const float*)xd + i0 * h->d, k, (float*)out.D + i0 * k, (int64_t*)out.I + i0 * k));
-    }
-    h->stat_nq += (uint64_t)n;                                  // IndexPQ.cpp:139-140, :200-201, :353-354
-    h->stat_ncode += (uint64_t)n * (uint64_t)h->ntotal;
-    return out.finish(&h->st);
+    return one_search(
+        h, n, x, (size_t)h->d * 4, k, D, I, P0.page,
+        [&](int64_t ni, const void* xd, float* Dd, int64_t* Id) { return pq_search_page(h, ni, (const float*)xd, k, Dd, Id); },
+        [&] {
+            h->stat_nq += (uint64_t)n;                              // IndexPQ.cpp:139-140, :200-201, :353-354
+            h->stat_ncode += (uint64_t)n * (uint64_t)h->ntotal;
+        });
 }
 
 // what the scan reads for these queries: out[n][M][ksub] [h|d] -- compute_distance_tables / compute_inner_prod_tables, under
@@ -297,13 +228,11 @@ int vlq_pq_search(vlq_pq_t h, int64_t n, const float* x, int k, float* D, int64_
 int vlq_pq_query_tables(vlq_pq_t h, int64_t n, const float* x, float* out) {
     TRY(pq_check_queries(h, n, x, out));
     if (n == 0) return VLQ_OK;
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void* xd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
     TRY(pq_prepare_dev(h, n, (const float*)xd));
-    HIP_TRY(hipMemcpyAsync(out, h->ws_qtab.p, (size_t)n * h->M * h->ksub * 4, hipMemcpyDefault, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    return VLQ_OK;
+    return one_fetch(&h->ctx, out, h->ws_qtab.p, (size_t)n * h->M * h->ksub * 4);
 }
 
 // the queries' codes: compute_code_from_distance_table under the polysemous types (IndexPQ.cpp:279-283), compute_codes under
@@ -312,48 +241,32 @@ int vlq_pq_query_codes(vlq_pq_t h, int64_t n, const float* x, uint8_t* out) {
     TRY(pq_check_queries(h, n, x, out));
     if (h->search_type == vlq::kPqST_PQ) return fail(VLQ_ERR_STATE, "ST_PQ reads no query codes");
     if (n == 0) return VLQ_OK;
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     const void* xd;
-    TRY(stage_in(&h->st, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
     TRY(pq_prepare_dev(h, n, (const float*)xd));
-    HIP_TRY(hipMemcpyAsync(out, h->ws_qcodes.p, (size_t)n * h->M, hipMemcpyDefault, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    return VLQ_OK;
+    return one_fetch(&h->ctx, out, h->ws_qcodes.p, (size_t)n * h->M);
 }
 
 // IndexPQStats (IndexPQ.h:119-127) of this handle since the last reset
 int vlq_pq_stats(vlq_pq_t h, uint64_t* nq, uint64_t* ncode, uint64_t* n_hamming_pass, int reset) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    TRY(set_dev(&h->st));
+    TRY(set_dev(&h->ctx));
     unsigned long long np = 0;      // read and cleared on the handle's stream: a legacy-stream clear is not ordered before the next search
-    HIP_TRY(hipMemcpyAsync(&np, h->n_pass.p, 8, hipMemcpyDeviceToHost, h->st.stream));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
+    HIP_TRY(hipMemcpyAsync(&np, h->n_pass.p, 8, hipMemcpyDeviceToHost, h->ctx.stream));
+    HIP_TRY(hipStreamSynchronize(h->ctx.stream));
     if (nq) *nq = h->stat_nq;
     if (ncode) *ncode = h->stat_ncode;
     if (n_hamming_pass) *n_hamming_pass = np;
     if (reset) {
-        HIP_TRY(hipMemsetAsync(h->n_pass.p, 0, 8, h->st.stream));
+        HIP_TRY(hipMemsetAsync(h->n_pass.p, 0, 8, h->ctx.stream));
         h->stat_nq = h->stat_ncode = 0;
     }
     return VLQ_OK;
 }
 
 // speed only: results never depend on it.  query_tile 0, 1, 2 or 4; slices 0 .. 64; 0 = the plan decides
-int vlq_pq_set_scan_split(vlq_pq_t h, int query_tile, int slices) {
-    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
-    if (query_tile != 0 && query_tile != 1 && query_tile != 2 && query_tile != 4) return fail(VLQ_ERR_INVALID, "query_tile %d (0, 1, 2 or 4)", query_tile);
-    if (slices < 0 || slices > vlq::kPqMaxSlices) return fail(VLQ_ERR_INVALID, "slices %d outside 0..%d", slices, vlq::kPqMaxSlices);
-    h->force_q = query_tile;
-    h->force_s = slices;
-    return VLQ_OK;
-}
-
-int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap) {
-    if (!h || !buf || cap < 1) return fail(VLQ_ERR_INVALID, "null argument");
-    TRY(set_dev(&h->st));
-    HIP_TRY(hipStreamSynchronize(h->st.stream));
-    snprintf(buf, (size_t)cap, "%s", h->last_scan[0] ? h->last_scan : "kernel=none");
-    return VLQ_OK;
-}
+int vlq_pq_set_scan_split(vlq_pq_t h, int query_tile, int slices) { return one_set_scan_split(h, query_tile, slices, vlq::kPqMaxSlices); }
+int vlq_pq_last_scan_info(vlq_pq_t h, char* buf, int cap) { return one_last_scan_info(h, buf, cap); }
 
 }  // extern "C"

@@ -628,7 +628,59 @@ class GpuIVFSQ(_GpuIVF):
         return super().last_scan_info()
 
 
-class GpuPQ:
+class _GpuOneList:
+    """What GpuPQ, GpuSQ, GpuFlat and GpuLSH share: the calls of the C ABI that differ in their prefix only (_PREFIX) -- the
+    handle's lifetime and stream, add, ntotal, reset, reserve_memory, search(x, k) and last_scan_info (csrc/one_list.h)."""
+
+    _PREFIX = None
+    _out = GpuIVFPQ._out
+
+    def _call(self, name, *args):
+        check(getattr(lib(), self._PREFIX + name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._PREFIX + "destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr or 0))
+
+    def add(self, x):
+        px, _a = _ptr(x, np.float32)
+        self._call("add", C.c_int64(x.shape[0]), px)
+
+    @property
+    def ntotal(self):
+        return int(getattr(lib(), self._PREFIX + "ntotal")(self._h))
+
+    def reset(self):
+        self._call("reset")
+
+    def reserve_memory(self, num_vecs):
+        self._call("reserve_memory", C.c_int64(num_vecs))
+
+    def search(self, x, k, D=None, I=None):
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        D = self._out(D, (n, k), np.float32, x)
+        I = self._out(I, (n, k), np.int64, x)
+        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def last_scan_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_scan_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
+class GpuPQ(_GpuOneList):
     """faiss::IndexPQ (IndexPQ.h:28-117; "PQx" of index_factory): every stored code is scored for every query.  metric "l2":
     ascending distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are scan
     positions.  search_type: "pq" (ADC), "sdc", "polysemous", "polysemous_generalize", or Search_type_t's number
@@ -636,7 +688,7 @@ class GpuPQ:
 
     METRICS = GpuIVFPQ.METRICS
     SEARCH_TYPES = {"pq": 0, "he": 1, "generalized_he": 2, "sdc": 3, "polysemous": 4, "polysemous_generalize": 5}   # IndexPQ::Search_type_t
-    _out = GpuIVFPQ._out
+    _PREFIX = "vlq_pq_"
 
     def __init__(self, d, M, nbits=8, metric="l2", device=0):
         self.d, self.M, self.nbits, self.device = d, M, nbits, device
@@ -649,24 +701,7 @@ class GpuPQ:
         self._search_type = 0
         self._polysemous_ht = nbits * M + 1
 
-    def _call(self, name, *args):
-        check(getattr(lib(), "vlq_pq_" + name)(self._h, *args))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_pq_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # --- state ------------------------------------------------------------
-    def set_stream(self, stream_ptr):
-        self._call("set_stream", C.c_void_p(stream_ptr or 0))
-
     def set_centroids(self, c):
         """ProductQuantizer::centroids [M][ksub][dsub]"""
         p, _k = _ptr(c, np.float32)
@@ -676,10 +711,6 @@ class GpuPQ:
         """IndexPQ::codes [ntotal][M] uint8; replaces the stored codes"""
         p, _k = _ptr(codes, np.uint8)
         self._call("set_codes", p, C.c_int64(codes.shape[0]))
-
-    def add(self, x):
-        px, _a = _ptr(x, np.float32)
-        self._call("add", C.c_int64(x.shape[0]), px)
 
     def encode(self, x):
         """the codes [n][M] add would store; nothing is stored"""
@@ -694,16 +725,6 @@ class GpuPQ:
         out = np.empty((ni, self.M), np.uint8)
         self._call("get_codes", C.c_int64(i0), C.c_int64(ni), out.ctypes.data_as(C.c_void_p))
         return out
-
-    @property
-    def ntotal(self):
-        return int(lib().vlq_pq_ntotal(self._h))
-
-    def reset(self):
-        self._call("reset")
-
-    def reserve_memory(self, num_vecs):
-        self._call("reserve_memory", C.c_int64(num_vecs))
 
     def _set_search(self, search_type, ht):
         st = self.SEARCH_TYPES.get(search_type, search_type)
@@ -729,14 +750,6 @@ class GpuPQ:
         self._set_search(self._search_type, ht)
 
     # --- search -----------------------------------------------------------
-    def search(self, x, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
-        return D, I
-
     def query_tables(self, x):
         """the tables the scan reads for x, [n][M][ksub] float32"""
         px, _a = _ptr(x, np.float32)
@@ -761,13 +774,8 @@ class GpuPQ:
         """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
         self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
 
-    def last_scan_info(self):
-        buf = C.create_string_buffer(256)
-        self._call("last_scan_info", buf, C.c_int(256))
-        return buf.value.decode()
 
-
-class GpuSQ:
+class GpuSQ(_GpuOneList):
     """faiss::IndexScalarQuantizer (IndexScalarQuantizer.h:82-120; "SQ8" / "SQ4" of index_factory): every stored code of 8 or 4
     bits per component is decoded and compared with every query.  qtype as for GpuIVFSQ.  The reference leaves its rows in
     heap order (it never reorders the heap in this search); here they come back sorted: metric "l2": ascending distances, then
@@ -776,7 +784,7 @@ class GpuSQ:
 
     METRICS = GpuIVFPQ.METRICS
     QTYPES = GpuIVFSQ.QTYPES
-    _out = GpuIVFPQ._out
+    _PREFIX = "vlq_sq_"
 
     def __init__(self, d, qtype, device=0, metric="l2"):
         self.d, self.device = d, device
@@ -789,23 +797,6 @@ class GpuSQ:
         self.uniform = self.qtype >= 2
         self.bits = 8 if self.qtype in (0, 2) else 4
         self.code_size = int(lib().vlq_sq_code_size(self._h))
-
-    def _call(self, name, *args):
-        check(getattr(lib(), "vlq_sq_" + name)(self._h, *args))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_sq_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr):
-        self._call("set_stream", C.c_void_p(stream_ptr or 0))
 
     def set_trained(self, trained):
         """ScalarQuantizer::trained: vmin[d] then vdiff[d] (two floats for the uniform types), host floats"""
@@ -833,10 +824,6 @@ class GpuSQ:
         p, _k = _ptr(codes, np.uint8)
         self._call("set_codes", p, C.c_int64(codes.shape[0]))
 
-    def add(self, x):
-        px, _a = _ptr(x, np.float32)
-        self._call("add", C.c_int64(x.shape[0]), px)
-
     def encode(self, x):
         """the codes [n][code_size] add would store; nothing is stored"""
         px, _a = _ptr(x, np.float32)
@@ -860,42 +847,19 @@ class GpuSQ:
         self._call("reconstruct", C.c_int64(i0), C.c_int64(n), _out_ptr(out, np.float32)[0])
         return out
 
-    @property
-    def ntotal(self):
-        return int(lib().vlq_sq_ntotal(self._h))
-
-    def reset(self):
-        self._call("reset")
-
-    def reserve_memory(self, num_vecs):
-        self._call("reserve_memory", C.c_int64(num_vecs))
-
-    def search(self, x, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
-        return D, I
-
     def set_scan_split(self, query_tile=0, slices=0):
         """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
         self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
 
-    def last_scan_info(self):
-        buf = C.create_string_buffer(256)
-        self._call("last_scan_info", buf, C.c_int(256))
-        return buf.value.decode()
 
-
-class GpuFlat:
+class GpuFlat(_GpuOneList):
     """faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (gpu::GpuIndexFlat): the exact brute-force index.  metric "l2": ascending
     squared distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are positions in
     the order of add.  Fewer than 20 queries with d % 4 == 0 take the reference's per-pair SSE order, everything else the fmaf
     chain of the GEMM path; the call's n decides, never a page's (include/vlq_ivfpq.h, vlq_flat_*)."""
 
     METRICS = GpuIVFPQ.METRICS
-    _out = GpuIVFPQ._out
+    _PREFIX = "vlq_flat_"
 
     def __init__(self, d, metric="l2", device=0):
         self.d, self.device = d, device
@@ -905,37 +869,6 @@ class GpuFlat:
         self.metric = metric
         check(lib().vlq_flat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.METRICS[metric])))
 
-    def _call(self, name, *args):
-        check(getattr(lib(), "vlq_flat_" + name)(self._h, *args))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_flat_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr):
-        self._call("set_stream", C.c_void_p(stream_ptr or 0))
-
-    def add(self, x):
-        px, _a = _ptr(x, np.float32)
-        self._call("add", C.c_int64(x.shape[0]), px)
-
-    @property
-    def ntotal(self):
-        return int(lib().vlq_flat_ntotal(self._h))
-
-    def reset(self):
-        self._call("reset")
-
-    def reserve_memory(self, num_vecs):
-        self._call("reserve_memory", C.c_int64(num_vecs))
-
     def reconstruct_n(self, i0=0, n=None, out=None):
         """the stored bits of vectors i0 .. i0 + n - 1, [n][d] float32 (out: a numpy array or a torch tensor to fill)"""
         n = self.ntotal - i0 if n is None else n
@@ -944,22 +877,9 @@ class GpuFlat:
         self._call("reconstruct_n", C.c_int64(i0), C.c_int64(n), _out_ptr(out, np.float32)[0])
         return out
 
-    def search(self, x, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
-        return D, I
-
     def scan_split(self, row_tile=0, slices=0):
         """speed only: query rows per workgroup of the fused scan (0, 32, 64, 128) and column slices (0 .. 64); 0 = the plan decides"""
         self._call("set_scan_split", C.c_int(row_tile), C.c_int(slices))
-
-    def last_scan_info(self):
-        buf = C.create_string_buffer(256)
-        self._call("last_scan_info", buf, C.c_int(256))
-        return buf.value.decode()
 
     # --- IndexRefineFlat's seam (IndexFlat.cpp:73-93, :245-260) -----------------
     def compute_distance_subset(self, x, labels, distances):
@@ -1000,7 +920,7 @@ def random_rotation(d, nbits, seed=5):
     return np.ascontiguousarray(q[:nbits, :d], dtype=np.float32)
 
 
-class GpuLSH:
+class GpuLSH(_GpuOneList):
     """faiss::IndexLSH (IndexLSH.h; "LSH" of index_factory): a vector becomes the sign bits of its (optionally rotated,
     optionally thresholded) components, search is the exhaustive Hamming scan.  Distances are the integer Hamming distances as
     float32, ascending by (distance, position), padded 2147483648.0 / -1.  Labels are positions in the order of add.
@@ -1008,7 +928,7 @@ class GpuLSH:
     reference's bits (include/vlq_ivfpq.h, vlq_lsh_*)."""
 
     metric = "l2"         # what a GpuRefineFlat over this index re-ranks by
-    _out = GpuIVFPQ._out
+    _PREFIX = "vlq_lsh_"
 
     def __init__(self, d, nbits, rotate_data=True, train_thresholds=False, device=0):
         self.d, self.nbits, self.device = d, nbits, device
@@ -1021,24 +941,7 @@ class GpuLSH:
         if self.rotate_data:
             self.set_rotation(random_rotation(d, nbits, seed=5))
 
-    def _call(self, name, *args):
-        check(getattr(lib(), "vlq_lsh_" + name)(self._h, *args))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().vlq_lsh_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # --- state ------------------------------------------------------------
-    def set_stream(self, stream_ptr):
-        self._call("set_stream", C.c_void_p(stream_ptr or 0))
-
     def set_rotation(self, A, b=None):
         """rrot.A [nbits][d] and rrot.b [nbits] (None: no bias)"""
         pa, _a = _ptr(A, np.float32)
@@ -1083,10 +986,6 @@ class GpuLSH:
         self._call("encode", C.c_int64(x.shape[0]), px, codes.ctypes.data_as(C.c_void_p))
         return codes
 
-    def add(self, x):
-        px, _a = _ptr(x, np.float32)
-        self._call("add", C.c_int64(x.shape[0]), px)
-
     def add_codes(self, codes):
         """ready-made codes [n][bytes_per_vec] uint8, appended as they are"""
         if codes.shape[1] != self.bytes_per_vec:
@@ -1101,25 +1000,7 @@ class GpuLSH:
         self._call("get_codes", C.c_int64(i0), C.c_int64(ni), out.ctypes.data_as(C.c_void_p))
         return out
 
-    @property
-    def ntotal(self):
-        return int(lib().vlq_lsh_ntotal(self._h))
-
-    def reset(self):
-        self._call("reset")
-
-    def reserve_memory(self, num_vecs):
-        self._call("reserve_memory", C.c_int64(num_vecs))
-
     # --- search -----------------------------------------------------------
-    def search(self, x, k, D=None, I=None):
-        n = x.shape[0]
-        px, _a = _ptr(x, np.float32)
-        D = self._out(D, (n, k), np.float32, x)
-        I = self._out(I, (n, k), np.int64, x)
-        self._call("search", C.c_int64(n), px, C.c_int(k), _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
-        return D, I
-
     def search_codes(self, qcodes, k, D=None, I=None):
         """hammings_knn of ready-made query codes [n][bytes_per_vec] uint8"""
         n = qcodes.shape[0]
@@ -1134,11 +1015,6 @@ class GpuLSH:
     def scan_split(self, query_tile=0, slices=0):
         """speed only: queries per workgroup (0, 1, 2, 4) and code slices (0 .. 64); 0 = the plan decides"""
         self._call("set_scan_split", C.c_int(query_tile), C.c_int(slices))
-
-    def last_scan_info(self):
-        buf = C.create_string_buffer(256)
-        self._call("last_scan_info", buf, C.c_int(256))
-        return buf.value.decode()
 
 
 VLQ_MAX_K = 1024      # include/vlq_ivfpq.h
