@@ -3,9 +3,14 @@
 // MFMA distance kernel + wave64 select behind vlq_ivfpq_coarse_search
 // (= knn_L2sqr, utils.cpp:935-946; under METRIC_INNER_PRODUCT knn_inner_product, utils.cpp:726-755, :790-829: the k largest
 // inner products, descending, the lower id first among equals -- vlq_ivfpq_set_metric, include/vlq_ivfpq.h).
+// range_search() is IndexFlat::range_search (IndexFlat.cpp:58-70) behind vlq_flat_range_search, against a private vlq_flat_t
+// that mirrors xb the way IndexRefineFlat's store does: it appends the rows added since the last call and starts over after
+// reset() or when the index holds fewer rows than it has seen (xb is public and index_io fills it directly: a freshly read
+// index has seen none).  A caller that rewrites xb in place must call reset() and add again.
 #pragma once
 #include <vector>
 
+#include "AuxIndexStructures.h"
 #include "Index.h"
 
 namespace faiss {
@@ -15,7 +20,10 @@ struct IndexFlat : Index {
 
   explicit IndexFlat(idx_t d, MetricType metric = METRIC_INNER_PRODUCT) : Index(d, metric) {}
   IndexFlat() {}
-  ~IndexFlat() override { if (h_) vlq_ivfpq_destroy(h_); }
+  ~IndexFlat() override {
+    if (h_) vlq_ivfpq_destroy(h_);
+    if (store_) vlq_flat_destroy(store_);
+  }
   IndexFlat(const IndexFlat&) = delete;
   IndexFlat& operator=(const IndexFlat&) = delete;
 
@@ -24,7 +32,7 @@ struct IndexFlat : Index {
     ntotal += n;
     dirty_ = true;
   }
-  void reset() override { xb.clear(); ntotal = 0; dirty_ = true; }
+  void reset() override { xb.clear(); ntotal = 0; dirty_ = true; mirrored_ = -1; }
 
   void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override {
     FAISS_THROW_IF_NOT_MSG(k >= 1 && k <= VLQ_MAX_NPROBE, "k outside 1..1024");
@@ -36,6 +44,17 @@ struct IndexFlat : Index {
     }
     sync_();
     VLQ_CHECK(vlq_ivfpq_coarse_search(h_, n, x, (int)k, distances, (int64_t*)labels));
+  }
+  /// Every stored vector with dis < radius (METRIC_L2) or ip > radius (METRIC_INNER_PRODUCT), per query in ascending
+  /// position.  The counts go through result->do_allocation() as in the reference, so an overloaded allocation is honoured.
+  void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override {
+    FAISS_THROW_IF_NOT_MSG(result && (idx_t)result->nq == n, "RangeSearchResult must be constructed for the n queries");
+    sync_store_();
+    std::vector<int64_t> lims((size_t)n + 1, 0);
+    VLQ_CHECK(vlq_flat_range_search(store_, n, x, radius, lims.data(), nullptr));
+    for (idx_t i = 0; i < n; i++) result->lims[i] = (size_t)(lims[i + 1] - lims[i]);
+    result->do_allocation();
+    VLQ_CHECK(vlq_flat_range_result(store_, result->distances, (int64_t*)result->labels));
   }
   void reconstruct(idx_t key, float* recons) const override {
     FAISS_THROW_IF_NOT(key >= 0 && key < ntotal);
@@ -54,8 +73,24 @@ struct IndexFlat : Index {
     VLQ_CHECK(vlq_ivfpq_set_coarse_centroids(h_, xb.data()));
     dirty_ = false;
   }
+  void sync_store_() const {
+    if (!store_) {
+      VLQ_CHECK(vlq_flat_create(&store_, device, d, (int)metric_type));
+      mirrored_ = 0;
+    }
+    if (mirrored_ < 0 || ntotal < mirrored_) {
+      VLQ_CHECK(vlq_flat_reset(store_));
+      mirrored_ = 0;
+    }
+    if (ntotal > mirrored_) {
+      VLQ_CHECK(vlq_flat_add(store_, ntotal - mirrored_, xb.data() + (size_t)mirrored_ * d));
+      mirrored_ = ntotal;
+    }
+  }
   mutable vlq_ivfpq_t h_ = nullptr;
   mutable bool dirty_ = true;
+  mutable vlq_flat_t store_ = nullptr;     // range_search's mirror of xb
+  mutable idx_t mirrored_ = 0;             // rows of xb the store holds; -1: start over
 };
 
 struct IndexFlatL2 : IndexFlat {

@@ -655,7 +655,9 @@ int vlq_sq_last_scan_info(vlq_sq_t h, char* buf, int cap);
  * and walks the database in column chunks behind a bounded matrix for larger k and on the small-batch path.
  * Limits: k in 1 .. VLQ_MAX_K (k > ntotal pads, ntotal == 0 gives padded rows), ntotal < 2^32 (the key's position field), any
  * d >= 1 on the GEMM path; the small-batch path holds one query in LDS (d up to about 30 000: VLQ_ERR_UNSUPPORTED beyond).
- * Not built: range_search, remove_ids, float16 storage.  Pointers [h|d]. */
+ * range_search is IndexFlat::range_search (IndexFlat.cpp:58-70; utils.cpp:1090-1262) under the same dispatch and with the same
+ * distances bit for bit; see vlq_flat_range_search below.
+ * Not built: remove_ids, float16 storage.  Pointers [h|d]. */
 typedef struct vlq_flat_s* vlq_flat_t;
 
 /* metric: 0 = inner product, 1 = L2 (MetricType of Index.h); any other value: VLQ_ERR_INVALID */
@@ -680,6 +682,26 @@ int vlq_flat_set_scan_split(vlq_flat_t h, int row_tile, int slices);
  *   "path=gemm route=fused kernel=knn_gemm_kernel rows=128 S=4 slice=250000 chunk=0 page=32768 lds=141824 join=1".
  * Synchronises the stream. */
 int vlq_flat_last_scan_info(vlq_flat_t h, char* buf, int cap);
+
+/* IndexFlat::range_search (IndexFlat.cpp:58-70): every stored vector with dis < radius (L2) or ip > radius (inner product, on
+ * the un-negated value) is a hit; both tests are strict, a NaN on either side is no hit, and an L2 distance of the GEMM path is
+ * not clamped (a slightly negative one is a hit at radius 0, as in the reference).  n < 20 && d % 4 == 0 takes range_search_sse's
+ * per-pair distances, everything else range_search_blas's expression with the fmaf chain, as vlq_flat_search does; the n of the
+ * WHOLE call decides.  A query's hits come out in ascending position (a label is a position in the store), so a stored
+ * duplicate comes back twice, the lower position first.  There is no k, no cap on the hits and no statistics.
+ * x[n*d], lims[n+1] [h|d]: the exclusive prefix sums of the hits per query; *total = lims[n] (host, may be NULL).  n == 0 writes
+ * lims[0] = 0; ntotal == 0 gives all-zero lims without a launch.  The hits stay in the handle until the next range search,
+ * reset or destroy (an add in between does not change them).  Every range search call drops the previous hits before it looks
+ * at its arguments.  Two passes (count, fill) over the store with one exclusive scan between them; scratch is 12 bytes per
+ * (query, column slice), never a term in n * ntotal; the result blocks are exactly 4 * total and 8 * total bytes (a failed
+ * allocation: VLQ_ERR_INVALID "out of memory").  Synchronises the stream once between the passes, to read the total.
+ * vlq_flat_set_scan_split forces the row tile and the slices here too; results never depend on it.  Afterwards
+ * vlq_flat_last_scan_info reads "path=gemm kernel=range_gemm_kernel rows=64 S=8 slice=125000 page=32768 lds=56832".
+ * Limits: ntotal < 2^32, any d >= 1 on the GEMM path; the small-batch path holds one query in LDS (VLQ_ERR_UNSUPPORTED beyond). */
+int vlq_flat_range_search(vlq_flat_t h, int64_t n, const float* x, float radius, int64_t* lims, int64_t* total);
+/* RangeSearchResult::distances / labels of the last range search: D[total] (the inner product un-negated), I[total] [h|d], either
+ * may be NULL; may be called again.  Synchronises the stream. */
+int vlq_flat_range_result(vlq_flat_t h, float* D, int64_t* I);
 
 /* --- IndexRefineFlat: exact re-ranking of a shortlist (IndexFlat.h:103-140, IndexFlat.cpp:149-269) ---
  * A label is a position in the flat store; a label < 0 is skipped (the reference's `continue`, utils.cpp:984, :1004).  The

@@ -46,7 +46,7 @@ SYMBOLS = [
     # flat exact k-NN (vlq_flat_t)
     "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
     "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
-    "vlq_flat_compute_distance_subset", "vlq_flat_refine", "vlq_flat_last_refine_info",
+    "vlq_flat_compute_distance_subset", "vlq_flat_refine", "vlq_flat_last_refine_info", "vlq_flat_range_search", "vlq_flat_range_result",
     # LSH: sign-bit codes and Hamming k-NN (vlq_lsh_t)
     "vlq_lsh_create", "vlq_lsh_destroy", "vlq_lsh_set_stream", "vlq_lsh_set_rotation", "vlq_lsh_set_thresholds", "vlq_lsh_apply",
     "vlq_lsh_encode", "vlq_lsh_add", "vlq_lsh_add_codes", "vlq_lsh_get_codes", "vlq_lsh_ntotal", "vlq_lsh_reset",

@@ -4,27 +4,8 @@
 // index's statistics.
 #include "flat_plan.h"
 #include "ivf_shell.h"
+#include "range_hits.h"
 #include "range_plan.h"
-
-namespace {
-
-// RangeSearchResult::distances / labels of the last range search: blocks of exactly 4 * total and 8 * total bytes
-struct RangeHits {
-    float* D = nullptr;
-    int64_t* I = nullptr;
-    int64_t total = 0;
-    RangeHits() = default;
-    RangeHits(const RangeHits&) = delete;
-    RangeHits& operator=(const RangeHits&) = delete;
-    ~RangeHits() { drop(); }
-    void drop() {
-        if (D) (void)hipFree(D);
-        if (I) (void)hipFree(I);
-        D = nullptr; I = nullptr; total = 0;
-    }
-};
-
-}  // namespace
 
 struct vlq_ivfflat_s : IvfShell {      // stats: [0] distances computed (u64), [1] bad key flag (int), [2] lists visited (u64)
     uint64_t stat_nq = 0;

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "knn_plan.h"
+#include "knn_range_plan.h"
 #include "pq_plan.h"
 #include "refine_flat_plan.h"
 #include "scan_plan.h"
@@ -408,6 +409,33 @@ struct KnnArgs {
     bool ip;
 };
 bool launch_knn(const KnnArgs& a, const KnnPlan& P, hipStream_t s);
+
+// Range search of the flat index (faiss::IndexFlat::range_search, IndexFlat.cpp:58-70, utils.cpp:1090-1262; scan_range_knn.hip),
+// one of its two passes over one page (nq <= P.page) of queries xq [nq][d]; plan_knn_range (knn_range_plan.h) decides for the
+// WHOLE call.  counts / base: the page's rows of the call's [nq_call][P.S] hit counts and first slots.
+//   fill = false  counts[q][s] = hits of query q in slice s
+//   fill = true   hit r of (q, s) in ascending position goes to D / I [base[q][s] + r] (D: the distance, the inner product
+//                 un-negated; I: the position); a slot >= total is never written
+// yn, qn as for launch_knn.  false: not built.
+struct KnnRangeArgs {
+    const float* xb;
+    const float* yn;
+    const float* xq;
+    const float* qn;
+    uint32_t* counts;
+    const int64_t* base;
+    float* D;
+    int64_t* I;
+    int64_t nq, ntotal, total;
+    int d;
+    float radius;
+    bool ip;
+};
+bool launch_knn_range(const KnnRangeArgs& a, const KnnRangePlan& P, bool fill, hipStream_t s);
+// base[i] = c[0] + .. + c[i-1] for the n counts at c (rocPRIM's exclusive scan); tmp == nullptr: only *tmp_bytes is set
+hipError_t knn_range_scan(const uint32_t* c, int64_t* base, int64_t n, void* tmp, size_t* tmp_bytes, hipStream_t s);
+// lims[q] = base[q * S] for q = 0 .. n (the last one is the total)
+void launch_knn_range_lims(const int64_t* base, int64_t n, int S, int64_t* lims, hipStream_t s);
 
 // counting sort of query ids by nearest coarse centroid: hist [nlist+1] ints scratch
 // ints of scratch launch_query_order needs in `hist`: 2 x this

@@ -2,9 +2,12 @@
 // Host-side orchestration only.  The device context, the one list -- the vectors as rows of 4 * d bytes, as IVFFlat stores its
 // lists --, the paged search and the reader of the stored vectors are the one-list shell's (one_list.h); here are what is
 // IndexFlat's own: the squared norms in a buffer that grows with the list (launch_row_norms over the appended rows only), the
-// call's plan and the scan of one page under it (scan_knn.hip, knn_plan.h), and IndexRefineFlat's seam (refine_flat.hip).
+// call's plan and the scan of one page under it (scan_knn.hip, knn_plan.h), the two passes of range_search and the hits it
+// leaves in the handle (scan_range_knn.hip, knn_range_plan.h), and IndexRefineFlat's seam (refine_flat.hip).
 #include "knn_plan.h"
+#include "knn_range_plan.h"
 #include "one_list.h"
+#include "range_hits.h"
 
 struct vlq_flat_s : OneListShell {      // (force_tile: the row tile)
     int d = 0;
@@ -15,6 +18,8 @@ struct vlq_flat_s : OneListShell {      // (force_tile: the row tile)
     // vlq_flat_compute_distance_subset / vlq_flat_refine: the staged labels and base distances, the device flag of a label >= ntotal
     DevBuf ws_rl, ws_rD, refine_bad;
     char last_refine[160] = "";
+    RangeHits range;              // vlq_flat_range_search: held until the next range search, reset or destroy
+    DevBuf ws_counts, ws_base, ws_scan, ws_lims;      // its counts and slots [n S + 1], rocPRIM's storage, lims of a host caller
 };
 
 namespace {
@@ -108,6 +113,74 @@ int refine_flat_plan_fail(vlq_flat_t h, int k_base, int k, const vlq::RefineFlat
     return fail(P.err == 2 ? VLQ_ERR_UNSUPPORTED : VLQ_ERR_INVALID, "flat refine of d=%d, k_base=%d, k=%d (at most %d): %s", h->d, k_base, k, VLQ_MAX_K, P.why);
 }
 
+// IndexFlat::range_search on device queries: the count pass over every page, the one scan, the blocks of exactly `total`
+// hits, the fill pass over every page.  The call synchronises between the passes, to read the total.
+int flat_range_dev(vlq_flat_t h, const vlq::KnnRangePlan& P, int64_t n, const float* xd, float radius, int64_t* lims, int64_t* total) {
+    hipStream_t s = h->ctx.stream;
+    const bool ip = h->metric == 0;
+    const bool dev_lims = is_device_ptr(lims);
+    int64_t* ld = lims;
+    if (!dev_lims) {
+        TRY(h->ws_lims.reserve((size_t)(n + 1) * 8));
+        ld = h->ws_lims.as<int64_t>();
+    }
+    const size_t cells = (size_t)n * P.S + 1;           // (the last count is 0: its slot is the total)
+    TRY(h->ws_counts.reserve(cells * 4));
+    TRY(h->ws_base.reserve(cells * 8));
+    vlq::KnnRangeArgs a = {};
+    a.xb = h->lists.codes.as<float>();
+    a.yn = h->norms.as<float>();
+    a.ntotal = h->ntotal; a.d = h->d; a.radius = radius; a.ip = ip;
+    if (P.path == vlq::kKnnGemm && !ip) {
+        TRY(h->ws_qn.reserve((size_t)n * 4));
+        vlq::launch_row_norms(xd, n, h->d, h->ws_qn.as<float>(), s);
+    }
+    auto pass = [&](bool fill) {
+        for (int64_t i0 = 0; i0 < n; i0 += P.page) {
+            a.nq = std::min(P.page, n - i0);
+            a.xq = xd + (size_t)i0 * h->d;
+            a.qn = (P.path == vlq::kKnnGemm && !ip) ? h->ws_qn.as<float>() + i0 : nullptr;
+            a.counts = h->ws_counts.as<uint32_t>() + (size_t)i0 * P.S;
+            a.base = h->ws_base.as<int64_t>() + (size_t)i0 * P.S;
+            if (!vlq::launch_knn_range(a, P, fill, s))
+                return fail(VLQ_ERR_UNSUPPORTED, "flat range search: no kernel for rows=%d (%s)", P.rows, vlq::knn_path_name(P.path));
+            HIP_TRY(hipGetLastError());
+        }
+        return (int)VLQ_OK;
+    };
+    HIP_TRY(hipMemsetAsync(h->ws_counts.as<uint32_t>() + (cells - 1), 0, 4, s));
+    TRY(pass(false));
+    size_t scan_bytes = 0;
+    HIP_TRY(vlq::knn_range_scan(h->ws_counts.as<uint32_t>(), h->ws_base.as<int64_t>(), (int64_t)cells, nullptr, &scan_bytes, s));
+    TRY(h->ws_scan.reserve(std::max(scan_bytes, (size_t)16)));
+    HIP_TRY(vlq::knn_range_scan(h->ws_counts.as<uint32_t>(), h->ws_base.as<int64_t>(), (int64_t)cells, h->ws_scan.p, &scan_bytes, s));
+    vlq::launch_knn_range_lims(h->ws_base.as<int64_t>(), n, P.S, ld, s);
+    HIP_TRY(hipGetLastError());
+    int64_t tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, h->ws_base.as<int64_t>() + (cells - 1), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    snprintf(h->last_scan, sizeof(h->last_scan), "path=%s kernel=%s rows=%d S=%d slice=%lld page=%lld lds=%zu", vlq::knn_path_name(P.path),
+             P.path == vlq::kKnnDirect ? "range_direct_kernel" : "range_gemm_kernel", P.rows, P.S, (long long)P.slice_len, (long long)P.page, P.lds);
+    if (tot > 0) {
+        if (hipMalloc((void**)&h->range.D, (size_t)tot * 4) != hipSuccess || hipMalloc((void**)&h->range.I, (size_t)tot * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            h->range.drop();
+            return fail(VLQ_ERR_INVALID, "out of memory (%lld hits of a range search)", (long long)tot);
+        }
+        h->range.total = tot;
+        a.D = h->range.D;
+        a.I = h->range.I;
+        a.total = tot;
+        TRY(pass(true));
+    }
+    if (!dev_lims) {
+        HIP_TRY(hipMemcpyAsync(lims, ld, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (total) *total = tot;
+    return VLQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -153,7 +226,11 @@ int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x) {
 }
 
 int64_t vlq_flat_ntotal(vlq_flat_t h) { return one_ntotal(h); }
-int vlq_flat_reset(vlq_flat_t h) { return one_reset(h); }       // IndexFlat::reset (IndexFlat.cpp:35-38)
+int vlq_flat_reset(vlq_flat_t h) {       // IndexFlat::reset (IndexFlat.cpp:35-38)
+    TRY(one_reset(h));
+    h->range.drop();
+    return VLQ_OK;
+}
 
 int vlq_flat_reserve_memory(vlq_flat_t h, int64_t num_vecs) {
     if (!h || num_vecs < 0) return fail(VLQ_ERR_INVALID, "bad argument: num_vecs=%lld", (long long)num_vecs);
@@ -188,6 +265,41 @@ int vlq_flat_search(vlq_flat_t h, int64_t n, const float* x, int k, float* D, in
                      P.route == vlq::kKnnFused ? "knn_gemm_kernel" : P.path == vlq::kKnnDirect ? "knn_direct_kernel" : "coarse_dist+knn_select_kernel",
                      P.rows, P.S, (long long)P.slice_len, (long long)P.chunk, (long long)P.page, P.lds, P.join ? 1 : 0);
         });
+}
+
+// IndexFlat::range_search (IndexFlat.cpp:58-70).  The hits of the last call go before any argument is looked at, so that a
+// call that is refused -- for whatever reason -- leaves an empty result in the handle, never the previous call's.
+int vlq_flat_range_search(vlq_flat_t h, int64_t n, const float* x, float radius, int64_t* lims, int64_t* total) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    TRY(set_dev(&h->ctx));
+    h->range.drop();
+    if (total) *total = 0;
+    if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
+    if (!lims || (n > 0 && !x)) return fail(VLQ_ERR_INVALID, "null buffer");
+    hipStream_t s = h->ctx.stream;
+    if (n == 0 || h->ntotal == 0) {       // lims[0] = 0 resp. all-zero lims: no launch
+        if (is_device_ptr(lims)) HIP_TRY(hipMemsetAsync(lims, 0, (size_t)(n + 1) * 8, s));
+        else memset(lims, 0, (size_t)(n + 1) * 8);
+        return VLQ_OK;
+    }
+    // the dispatch and the plan are the call's (utils.cpp:1239-1262)
+    const vlq::KnnRangePlan P = vlq::plan_knn_range(n, h->ntotal, h->d, h->force_tile, h->force_s);
+    if (!P.ok) return fail(P.err == 2 ? VLQ_ERR_UNSUPPORTED : VLQ_ERR_INVALID, "flat range search of n=%lld, ntotal=%lld, d=%d: %s", (long long)n,
+                           (long long)h->ntotal, h->d, P.why);
+    const void* xd = nullptr;
+    TRY(stage_in(&h->ctx, x, (size_t)n * h->d * 4, h->ws_x, &xd));
+    return flat_range_dev(h, P, n, (const float*)xd, radius, lims, total);
+}
+
+int vlq_flat_range_result(vlq_flat_t h, float* D, int64_t* I) {
+    if (!h) return fail(VLQ_ERR_INVALID, "null handle");
+    if (h->range.total == 0) return VLQ_OK;
+    TRY(set_dev(&h->ctx));
+    hipStream_t s = h->ctx.stream;
+    if (D) HIP_TRY(hipMemcpyAsync(D, h->range.D, (size_t)h->range.total * 4, hipMemcpyDefault, s));
+    if (I) HIP_TRY(hipMemcpyAsync(I, h->range.I, (size_t)h->range.total * 8, hipMemcpyDefault, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VLQ_OK;
 }
 
 // speed only: results never depend on it

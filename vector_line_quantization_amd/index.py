@@ -868,6 +868,7 @@ class GpuFlat(_GpuOneList):
             raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
         self.metric = metric
         check(lib().vlq_flat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.METRICS[metric])))
+        self._range_total = 0         # hits the handle holds (range_search)
 
     def reconstruct_n(self, i0=0, n=None, out=None):
         """the stored bits of vectors i0 .. i0 + n - 1, [n][d] float32 (out: a numpy array or a torch tensor to fill)"""
@@ -880,6 +881,34 @@ class GpuFlat(_GpuOneList):
     def scan_split(self, row_tile=0, slices=0):
         """speed only: query rows per workgroup of the fused scan (0, 32, 64, 128) and column slices (0 .. 64); 0 = the plan decides"""
         self._call("set_scan_split", C.c_int(row_tile), C.c_int(slices))
+
+    def reset(self):
+        super().reset()
+        self._range_total = 0
+
+    # --- range search (IndexFlat.cpp:58-70) -------------------------------------
+    def range_search(self, x, radius):
+        """IndexFlat::range_search: every stored vector with dis < radius ("l2") or ip > radius ("ip"), per query in ascending
+        position; (lims [n + 1], D [total], I [total]), query i's hits are D / I [lims[i]:lims[i + 1]].  Outputs are on x's
+        device if x is a device tensor.  The radius goes as a C float: the loader sets no argtypes, and a bare Python float
+        would be passed as a double."""
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        lims = self._out(None, (n + 1,), np.int64, x)
+        total = C.c_int64()
+        self._range_total = 0          # (a failed call leaves an empty result in the handle)
+        self._call("range_search", C.c_int64(n), px, C.c_float(radius), _out_ptr(lims, np.int64)[0], C.byref(total))
+        self._range_total = total.value
+        return (lims,) + self.range_result(like=x)
+
+    def range_result(self, like=None):
+        """(D, I) of the last range search again (held until the next range search, reset or close); device tensors if
+        `like` is one"""
+        total = self._range_total
+        D = self._out(None, (total,), np.float32, like)
+        I = self._out(None, (total,), np.int64, like)
+        self._call("range_result", _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
 
     # --- IndexRefineFlat's seam (IndexFlat.cpp:73-93, :245-260) -----------------
     def compute_distance_subset(self, x, labels, distances):
