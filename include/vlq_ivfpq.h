@@ -363,8 +363,14 @@ int vlq_ivfpq_profile_read(vlq_ivfpq_t h, double ms[3], int64_t* calls, int rese
  * aborts the reference's search (:296-300, :346-350): reported as for vlq_ivfpq_search_preassigned (VLQ_ERR_INVALID from the
  * call with a host D or I, from the next vlq_ivfflat_stats() otherwise).
  * Limits: k <= VLQ_MAX_K, nprobe <= VLQ_MAX_NPROBE, 4 * d + 24 * nprobe within the kernel's LDS (d up to about 29 000):
- * VLQ_ERR_UNSUPPORTED otherwise, there is no other path.  float16 storage (GpuIndexIVFFlatConfig::useFloat16IVFStorage),
- * update_vectors and the direct map are not built.
+ * VLQ_ERR_UNSUPPORTED otherwise, there is no other path.  update_vectors and the direct map are not built.
+ * float16 storage (GpuIndexIVFFlatConfig::useFloat16IVFStorage; vlq_ivfflat_create_ex with storage = 1; csrc/scan_flat16.hip,
+ * csrc/scan_range_flat16.hip): the lists hold half(x), round to nearest even (half subnormals kept, values beyond the half
+ * range become +-inf: numpy's astype(float16)), 2 * d bytes per row.  The coarse assignment of an add is made on the fp32
+ * vector, the row is rounded when it is appended; the query stays fp32 and all arithmetic is fp32 in the same operation
+ * order, so the handle returns, bit for bit, what an fp32 handle over float(half(x)) returns: rows, padding, ties, statistics,
+ * the bad-key flag, k-NN and range search.  Every entry point below keeps fp32 at the boundary (set_lists and add round,
+ * get_list widens).
  * Range search (IndexIVFFlat::range_search, IndexIVF.cpp:401-449; csrc/scan_range_flat.hip): every stored vector of the
  * probed lists with dis < radius (L2) or ip > radius (inner product) -- both strict, a NaN radius or distance is no hit --
  * with the same distance bits as the k-NN scan.  The hits of a query stand in scan order: the probes in the order given,
@@ -377,6 +383,10 @@ typedef struct vlq_ivfflat_s* vlq_ivfflat_t;
 
 /* IndexIVFFlat::IndexIVFFlat (IndexIVF.cpp:204-209).  metric: MetricType of Index.h (0 = inner product, 1 = L2). */
 int vlq_ivfflat_create(vlq_ivfflat_t* out, int device, int d, int nlist, int metric);
+/* the same with the lists' storage: 0 = float32 (what vlq_ivfflat_create makes), 1 = float16; anything else VLQ_ERR_INVALID */
+int vlq_ivfflat_create_ex(vlq_ivfflat_t* out, int device, int d, int nlist, int metric, int storage);
+/* the storage the handle was created with (-1: null handle) */
+int vlq_ivfflat_storage(vlq_ivfflat_t h);
 void vlq_ivfflat_destroy(vlq_ivfflat_t h);
 /* as vlq_ivfpq_set_stream */
 int vlq_ivfflat_set_stream(vlq_ivfflat_t h, void* hip_stream);
@@ -426,7 +436,8 @@ int vlq_ivfflat_range_result(vlq_ivfflat_t h, float* D, int64_t* I);
 int vlq_ivfflat_stats(vlq_ivfflat_t h, uint64_t* nq, uint64_t* nlist_visited, uint64_t* ndis, int reset);
 /* Introspection, speed only: the kernel instantiation and read path of the last scan, as text:
  *   "kernel=scan_flat_kernel<1, L2> read=tile128 lds=40304"; after a range search
- *   "kernel=range_flat_kernel<L2> read=tile128 lds=37152".  Synchronises the stream. */
+ *   "kernel=range_flat_kernel<L2> read=tile128 lds=37152"; a float16 handle names its storage:
+ *   "kernel=scan_flat16_kernel<1, L2> store=f16 read=tile128 lds=40208" (read=row when d % 8 != 0).  Synchronises the stream. */
 int vlq_ivfflat_last_scan_info(vlq_ivfflat_t h, char* buf, int cap);
 
 /* ---- IVF scalar quantizer: inverted lists of 8- or 4-bit codes per component of the residual

@@ -24,7 +24,7 @@ SYMBOLS = [
     "vlq_ivfpq_set_polysemous_ht", "vlq_ivfpq_query_codes", "vlq_ivfpq_polysemous_stats",
     "vlq_ivfpq_set_metric", "vlq_ivfpq_get_metric",
     # IVFFlat (vlq_ivfflat_t)
-    "vlq_ivfflat_create", "vlq_ivfflat_destroy", "vlq_ivfflat_set_stream", "vlq_ivfflat_set_coarse_centroids",
+    "vlq_ivfflat_create", "vlq_ivfflat_create_ex", "vlq_ivfflat_storage", "vlq_ivfflat_destroy", "vlq_ivfflat_set_stream", "vlq_ivfflat_set_coarse_centroids",
     "vlq_ivfflat_set_lists", "vlq_ivfflat_add", "vlq_ivfflat_add_preassigned", "vlq_ivfflat_reserve_memory",
     "vlq_ivfflat_reclaim_memory", "vlq_ivfflat_ntotal", "vlq_ivfflat_list_length", "vlq_ivfflat_get_list", "vlq_ivfflat_reset",
     "vlq_ivfflat_coarse_search", "vlq_ivfflat_search", "vlq_ivfflat_search_preassigned", "vlq_ivfflat_stats",

@@ -1,7 +1,9 @@
 // C ABI of the IVFFlat index (include/vlq_ivfpq.h, vlq_ivfflat_*): faiss::IndexIVFFlat / gpu::GpuIndexIVFFlat on the device.
 // Host-side orchestration only, over the shell it shares with the scalar-quantizer index (ivf_shell.h: the coarse quantizer,
 // the lists, staging, the search bodies).  Here: rows of d floats (code_size = 4 * d), the scan of scan_flat.hip and the
-// index's statistics.
+// index's statistics.  A handle made with storage = 1 (vlq_ivfflat_create_ex) keeps its rows as halves (code_size = 2 * d):
+// fp32 rows are rounded on their way into the lists and widened on their way out (scan_flat16.hip's encoder / decoder), the
+// scans are scan_flat16.hip / scan_range_flat16.hip, and everything at the boundary stays fp32.
 #include "flat_plan.h"
 #include "ivf_shell.h"
 #include "range_hits.h"
@@ -9,6 +11,8 @@
 
 struct vlq_ivfflat_s : IvfShell {      // stats: [0] distances computed (u64), [1] bad key flag (int), [2] lists visited (u64)
     uint64_t stat_nq = 0;
+    int storage = vlq::kFlatStoreF32;  // FlatStore of flat_plan.h
+    DevBuf ws_half, ws_rows;           // float16 storage: the halves of an add batch; the fp32 rows of a list on their way out
     RangeHits range;                   // held until the next range search, reset or destroy
     DevBuf range_flag, ws_lims, ws_scan;   // the range scan's own bad-key flag (int); lims of a host caller; rocPRIM's storage
 };
@@ -19,12 +23,13 @@ constexpr size_t kFlatStatBytes = 24;
 const char* const kFlatBadKey = "a probe key >= nlist was passed to search_preassigned (IndexIVF.cpp:296-300, :346-350)";
 
 int flat_search_args(vlq_ivfflat_t f, int64_t n, const void* x, int nprobe, int k, const void* D, const void* I) {
-    return ivf_search_args(f, vlq::plan_flat_scan(f->d, nprobe, k).ok, "IVFFlat", n, x, nprobe, k, D, I);
+    return ivf_search_args(f, vlq::plan_flat_scan(f->d, nprobe, k, f->storage).ok, "IVFFlat", n, x, nprobe, k, D, I);
 }
 
 // IndexIVFFlat::search_preassigned on device buffers
 int flat_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* kd, int nprobe, int k, float* Dd, int64_t* Id) {
-    const vlq::FlatPlan P = vlq::plan_flat_scan(f->d, nprobe, k);
+    const bool f16 = f->storage == vlq::kFlatStoreF16;
+    const vlq::FlatPlan P = vlq::plan_flat_scan(f->d, nprobe, k, f->storage);
     vlq::ScanArgs a = {};
     a.codes = f->lists.codes.as<uint8_t>();
     a.ids = f->lists.ids.as<int64_t>();
@@ -37,21 +42,83 @@ int flat_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* kd
     a.bad_key = reinterpret_cast<int*>(f->stats.as<char>() + 8);
     a.nq = n; a.nprobe = nprobe; a.k = k; a.d = f->d; a.nlist = f->nlist;
     a.max_codes = 0; a.store_pairs = 0;
-    if (!vlq::launch_scan_flat(a, f->metric == 0, f->stats.as<unsigned long long>() + 2, f->cq->stream))
+    unsigned long long* visited = f->stats.as<unsigned long long>() + 2;
+    if (!(f16 ? vlq::launch_scan_flat16(a, f->metric == 0, visited, f->cq->stream) : vlq::launch_scan_flat(a, f->metric == 0, visited, f->cq->stream)))
         return fail(VLQ_ERR_UNSUPPORTED, "IVFFlat scan of d=%d with nprobe=%d, k=%d is not built", f->d, nprobe, k);
     HIP_TRY(hipGetLastError());
     f->stat_nq += (uint64_t)n;
-    snprintf(f->last_scan, sizeof(f->last_scan), "kernel=scan_flat_kernel<%d, %s> read=%s lds=%zu", P.kpl, f->metric == 0 ? "IP" : "L2",
-             vlq::flat_read_name(P.read), P.lay.bytes);
+    snprintf(f->last_scan, sizeof(f->last_scan), f16 ? "kernel=scan_flat16_kernel<%d, %s> store=f16 read=%s lds=%zu" : "kernel=scan_flat_kernel<%d, %s> read=%s lds=%zu",
+             P.kpl, f->metric == 0 ? "IP" : "L2", vlq::flat_read_name(P.read), P.lay.bytes);
     return VLQ_OK;
 }
 
-// IndexIVFFlat::add_core on device buffers: the rows are stored as they come
+// IndexIVFFlat::add_core on device buffers: the rows are stored as they come; float16 storage rounds them behind the
+// assignment, which is made on the fp32 vectors (the order of the reference's classifyAndAddVectors)
 int flat_add(vlq_ivfflat_t f, int64_t n, const float* x, const int64_t* xids, const int64_t* assign, bool preassigned) {
     return ivf_add(f, n, x, xids, assign, preassigned, [&](const float* xd, const int64_t* idd, const int64_t* ad) {
         TRY(ivf_assign(f, n, xd, &ad));
-        return ivf_append(f, n, ad, reinterpret_cast<const uint8_t*>(xd), idd);
+        if (f->storage != vlq::kFlatStoreF16) return ivf_append(f, n, ad, reinterpret_cast<const uint8_t*>(xd), idd);
+        TRY(f->ws_half.reserve((size_t)n * f->d * 2 + 16));
+        vlq::launch_flat16_encode(xd, n * f->d, f->ws_half.p, f->cq->stream);
+        HIP_TRY(hipGetLastError());
+        return ivf_append(f, n, ad, f->ws_half.as<uint8_t>(), idd);
     });
+}
+
+// set_lists of a float16 handle: ids and offsets as ever, the rows rounded into the lists' own array.  Device rows in one
+// launch; host rows in pages of kSetPageRows through the quantizer's staging buffer (a multiple of 8 rows: every page
+// starts 16-byte aligned on both sides), so no fp32 copy of the whole index ever stands on the device.
+constexpr int64_t kSetPageRows = 65536;
+int flat16_set_lists(vlq_ivfflat_t f, const float* vecs, const int64_t* ids, const int64_t* list_offsets) {
+    if (!f || !list_offsets) return fail(VLQ_ERR_INVALID, "null argument");
+    TRY(set_dev(f->cq));
+    hipStream_t s = f->cq->stream;
+    int64_t ntotal = 0;
+    const int rc = vlq::lists_load(f->lists, vecs, nullptr, ids, list_offsets, "list_offsets", vlq::kIvfLenLimit, s, &ntotal, true);
+    if (rc != VLQ_OK) return ntotal > 0 && (!vecs || !ids) ? fail(VLQ_ERR_INVALID, "null vecs/ids") : rc;
+    // (the lists now describe ntotal rows whose halves are still to be written)
+    const int64_t d = f->d;
+    const int enc = [&]() -> int {
+        if (is_device_ptr(vecs)) {
+            vlq::launch_flat16_encode(vecs, ntotal * d, f->lists.codes.p, s);
+        } else {
+            for (int64_t r0 = 0; r0 < ntotal; r0 += kSetPageRows) {
+                const int64_t nr = std::min(kSetPageRows, ntotal - r0);
+                const void* xd = nullptr;
+                TRY(stage_in(f->cq, vecs + r0 * d, (size_t)(nr * d) * 4, f->cq->ws_x, &xd));
+                vlq::launch_flat16_encode((const float*)xd, nr * d, f->lists.codes.as<uint8_t>() + r0 * d * 2, s);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        return VLQ_OK;
+    }();
+    if (enc != VLQ_OK) {        // a page that could not be staged or encoded: an empty index, never lists of unwritten rows
+        const std::string why = err_slot();
+        (void)vlq::lists_clear(f->lists, s);
+        (void)hipGetLastError();
+        err_slot() = why;
+        f->ntotal = 0;
+        return enc;
+    }
+    f->ntotal = ntotal;
+    return VLQ_OK;
+}
+
+// get_list of a float16 handle: the list's halves widened (exactly) into a workspace, fp32 rows out
+int flat16_get_list(vlq_ivfflat_t f, int list_id, float* vecs_out, int64_t* ids_out) {
+    int64_t len = 0;
+    TRY(ivf_list_length(f, list_id, &len));
+    TRY(ivf_get_list(f, list_id, nullptr, ids_out));
+    if (!vecs_out || len == 0) return VLQ_OK;
+    hipStream_t s = f->cq->stream;
+    const size_t n = (size_t)len * f->d;
+    TRY(f->ws_rows.reserve(n * 4));
+    vlq::launch_flat16_decode(f->lists.codes.as<uint8_t>() + (size_t)f->lists.h_off[(size_t)list_id] * f->d * 2, (int64_t)n, f->ws_rows.as<float>(), s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(vecs_out, f->ws_rows.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VLQ_OK;
 }
 
 const char* const kRangeBadKey = "a probe key < 0 or >= nlist was passed to range_search (IndexIVF.cpp:421-425)";
@@ -62,7 +129,7 @@ int range_args(vlq_ivfflat_t f, int64_t n, const void* x, int nprobe, const void
     if (nprobe < 1) return fail(VLQ_ERR_INVALID, "nprobe=%d must be positive", nprobe);
     if (nprobe > VLQ_MAX_NPROBE) return fail(VLQ_ERR_UNSUPPORTED, "nprobe=%d beyond %d", nprobe, VLQ_MAX_NPROBE);
     if (n > vlq::kRangeMaxQueries) return fail(VLQ_ERR_UNSUPPORTED, "n=%lld beyond %lld queries of one range search", (long long)n, vlq::kRangeMaxQueries);
-    if (!vlq::plan_flat_range(f->d, nprobe).ok)
+    if (!vlq::plan_flat_range(f->d, nprobe, f->storage).ok)
         return fail(VLQ_ERR_UNSUPPORTED, "IVFFlat range scan of d=%d with nprobe=%d does not fit the kernel's LDS", f->d, nprobe);
     return VLQ_OK;
 }
@@ -89,7 +156,9 @@ int range_empty(vlq_ivfflat_t f, int64_t* lims, int64_t* total) {
 // statistic counters are not touched (the reference's range_search keeps none).
 int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* kd, int nprobe, float radius, int64_t* lims, int64_t* total) {
     hipStream_t s = f->cq->stream;
-    const vlq::RangePlan P = vlq::plan_flat_range(f->d, nprobe);
+    const bool f16 = f->storage == vlq::kFlatStoreF16;
+    const vlq::RangePlan P = vlq::plan_flat_range(f->d, nprobe, f->storage);
+    const auto launch = f16 ? vlq::launch_range_flat16 : vlq::launch_range_flat;
     const bool dev_lims = is_device_ptr(lims);
     int64_t* ld = lims;
     if (!dev_lims) {
@@ -109,7 +178,7 @@ int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* k
     const bool ip = f->metric == 0;
     HIP_TRY(hipMemsetAsync(a.bad_key, 0, sizeof(int), s));
     HIP_TRY(hipMemsetAsync(ld, 0, 8, s));
-    if (!vlq::launch_range_flat(a, ip, radius, ld, false, s))
+    if (!launch(a, ip, radius, ld, false, s))
         return fail(VLQ_ERR_UNSUPPORTED, "IVFFlat range scan of d=%d with nprobe=%d is not built", f->d, nprobe);
     HIP_TRY(hipGetLastError());
     size_t scan_bytes = 0;
@@ -121,8 +190,8 @@ int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* k
     HIP_TRY(hipMemcpyAsync(&tot, ld + n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&bad, a.bad_key, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    snprintf(f->last_scan, sizeof(f->last_scan), "kernel=range_flat_kernel<%s> read=%s lds=%zu", ip ? "IP" : "L2", vlq::flat_read_name(P.read),
-             P.lay.bytes);
+    snprintf(f->last_scan, sizeof(f->last_scan), f16 ? "kernel=range_flat16_kernel<%s> store=f16 read=%s lds=%zu" : "kernel=range_flat_kernel<%s> read=%s lds=%zu",
+             ip ? "IP" : "L2", vlq::flat_read_name(P.read), P.lay.bytes);
     if (bad) return fail(VLQ_ERR_INVALID, "%s", kRangeBadKey);
     if (tot > 0) {
         if (hipMalloc((void**)&f->range.D, (size_t)tot * 4) != hipSuccess || hipMalloc((void**)&f->range.I, (size_t)tot * 8) != hipSuccess) {
@@ -133,7 +202,7 @@ int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* k
         f->range.total = tot;
         a.D = f->range.D;
         a.I = f->range.I;
-        (void)vlq::launch_range_flat(a, ip, radius, ld, true, s);
+        (void)launch(a, ip, radius, ld, true, s);
         HIP_TRY(hipGetLastError());
     }
     if (!dev_lims) {
@@ -149,24 +218,32 @@ int range_scan_dev(vlq_ivfflat_t f, int64_t n, const float* xd, const int64_t* k
 extern "C" {
 
 int vlq_ivfflat_create(vlq_ivfflat_t* out, int device, int d, int nlist, int metric) {
+    return vlq_ivfflat_create_ex(out, device, d, nlist, metric, vlq::kFlatStoreF32);
+}
+
+int vlq_ivfflat_create_ex(vlq_ivfflat_t* out, int device, int d, int nlist, int metric, int storage) {
     if (!out) return fail(VLQ_ERR_INVALID, "null out");
     *out = nullptr;
+    if (storage != vlq::kFlatStoreF32 && storage != vlq::kFlatStoreF16) return fail(VLQ_ERR_INVALID, "storage %d (0 = float32, 1 = float16)", storage);
     if (d <= 0 || nlist <= 0) return fail(VLQ_ERR_INVALID, "d, nlist must be positive");
     if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
     if ((int64_t)d * 4 > (int64_t)(1 << 30)) return fail(VLQ_ERR_UNSUPPORTED, "d=%d too large", d);
     vlq_ivfflat_s* f = new (std::nothrow) vlq_ivfflat_s();
     if (!f) return fail(VLQ_ERR_INVALID, "out of memory");
-    const int rc = ivf_init(f, device, d, nlist, metric, 4 * d, kFlatStatBytes);
+    f->storage = storage;
+    const int rc = ivf_init(f, device, d, nlist, metric, vlq::flat_code_size(d, storage), kFlatStatBytes);
     if (rc != VLQ_OK) { vlq_ivfflat_destroy(f); return rc; }
     *out = f;
     return VLQ_OK;
 }
 
 void vlq_ivfflat_destroy(vlq_ivfflat_t f) { ivf_destroy(f); }
+int vlq_ivfflat_storage(vlq_ivfflat_t f) { return f ? f->storage : -1; }
 int vlq_ivfflat_set_stream(vlq_ivfflat_t f, void* hip_stream) { return ivf_set_stream(f, hip_stream); }
 int vlq_ivfflat_set_coarse_centroids(vlq_ivfflat_t f, const float* centroids) { return ivf_set_coarse_centroids(f, centroids); }
 
 int vlq_ivfflat_set_lists(vlq_ivfflat_t f, const float* vecs, const int64_t* ids, const int64_t* list_offsets) {
+    if (f && f->storage == vlq::kFlatStoreF16) return flat16_set_lists(f, vecs, ids, list_offsets);
     return ivf_set_lists(f, vecs, ids, list_offsets, "null vecs/ids");
 }
 
@@ -185,7 +262,10 @@ int vlq_ivfflat_reserve_memory(vlq_ivfflat_t f, int64_t num_vecs) { return ivf_r
 int vlq_ivfflat_reclaim_memory(vlq_ivfflat_t f, uint64_t* bytes_reclaimed) { return ivf_reclaim_memory(f, bytes_reclaimed); }
 int64_t vlq_ivfflat_ntotal(vlq_ivfflat_t f) { return f ? f->ntotal : -1; }
 int vlq_ivfflat_list_length(vlq_ivfflat_t f, int list_id, int64_t* len) { return ivf_list_length(f, list_id, len); }
-int vlq_ivfflat_get_list(vlq_ivfflat_t f, int list_id, float* vecs_out, int64_t* ids_out) { return ivf_get_list(f, list_id, vecs_out, ids_out); }
+int vlq_ivfflat_get_list(vlq_ivfflat_t f, int list_id, float* vecs_out, int64_t* ids_out) {
+    if (f && f->storage == vlq::kFlatStoreF16) return flat16_get_list(f, list_id, vecs_out, ids_out);
+    return ivf_get_list(f, list_id, vecs_out, ids_out);
+}
 int vlq_ivfflat_reset(vlq_ivfflat_t f) {
     TRY(ivf_reset(f));
     f->range.drop();

@@ -12,7 +12,19 @@ namespace vlq {
 //     one dwordx4 each (a wave instruction covers 8 rows x 128 B: whole lines, each crossing from memory once per (query,
 //     list)); the 64 x 128 B tile is turned through the wave's LDS area so that every lane then owns one row.
 //   kFlatReadDword: d % 4 != 0.  Rows are not 16-byte aligned; every lane reads its own row dword by dword.
-enum FlatRead { kFlatReadTile128 = 0, kFlatReadDword = 1 };
+//   kFlatReadRow: float16 storage, d % 8 != 0.  Every lane reads its own row of halves (flat16_dist.cuh).
+enum FlatRead { kFlatReadTile128 = 0, kFlatReadDword = 1, kFlatReadRow = 2 };
+
+// How the lists hold a component (vlq_ivfflat_create_ex): fp32 as given, or half(x), round to nearest even
+// (GpuIndexIVFFlatConfig::useFloat16IVFStorage).  A float16 row is read by scan_flat16.hip / scan_range_flat16.hip; a
+// 128-byte piece then holds 64 components, the LDS tile is the same 64 x (128 + 16) bytes and the query stays fp32, so the
+// layout does not depend on the storage: only the read path does (tile128 iff rows are 16-byte aligned, d % 8 == 0).
+enum FlatStore { kFlatStoreF32 = 0, kFlatStoreF16 = 1 };
+inline int flat_read_path(int d, int storage) {
+    if (storage == kFlatStoreF16) return d % 8 == 0 ? kFlatReadTile128 : kFlatReadRow;
+    return d % 4 == 0 ? kFlatReadTile128 : kFlatReadDword;
+}
+inline int flat_code_size(int d, int storage) { return (storage == kFlatStoreF16 ? 2 : 4) * d; }
 
 constexpr int kFlatMaxProbes = 1024;      // VLQ_MAX_NPROBE
 constexpr int kFlatMaxK = 1024;           // VLQ_MAX_K
@@ -42,17 +54,17 @@ inline FlatLayout flat_layout(int nprobe, int k, int d) {
     return l;
 }
 
-inline FlatPlan plan_flat_scan(int d, int nprobe, int k) {
+inline FlatPlan plan_flat_scan(int d, int nprobe, int k, int storage = kFlatStoreF32) {
     FlatPlan p;
     if (d < 1 || nprobe < 1 || nprobe > kFlatMaxProbes || k < 1 || k > kFlatMaxK) return p;
     p.lay = flat_layout(nprobe, k, d);
     if (p.lay.bytes > kFlatLdsLimit) return p;
     p.kpl = k <= 64 ? 1 : k <= 256 ? 4 : 16;
-    p.read = d % 4 == 0 ? kFlatReadTile128 : kFlatReadDword;
+    p.read = flat_read_path(d, storage);
     p.ok = true;
     return p;
 }
 
-inline const char* flat_read_name(int read) { return read == kFlatReadTile128 ? "tile128" : "dword"; }
+inline const char* flat_read_name(int read) { return read == kFlatReadTile128 ? "tile128" : read == kFlatReadRow ? "row" : "dword"; }
 
 }  // namespace vlq

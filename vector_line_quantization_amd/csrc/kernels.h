@@ -328,6 +328,14 @@ bool launch_range_flat(const ScanArgs& a, bool inner_product, float radius, int6
 // counts to limits, in place: v[i] += v[0] + .. + v[i-1] for the n values at v (rocPRIM's scan).  tmp == nullptr: only
 // *tmp_bytes, the temporary storage the call needs, is set.
 hipError_t range_lims_scan(int64_t* v, int64_t n, void* tmp, size_t* tmp_bytes, hipStream_t s);
+// The same two scans over float16 lists (GpuIndexIVFFlatConfig::useFloat16IVFStorage; scan_flat16.hip, scan_range_flat16.hip):
+// a.codes holds rows of a.d halves, everything else is as above and the arithmetic is fp32, so the rows are those of the fp32
+// scans over float(half(x)) bit for bit.  Plans: plan_flat_scan / plan_flat_range with kFlatStoreF16.
+bool launch_scan_flat16(const ScanArgs& a, bool inner_product, unsigned long long* nlist_visited, hipStream_t s);
+bool launch_range_flat16(const ScanArgs& a, bool inner_product, float radius, int64_t* lims, bool fill, hipStream_t s);
+// `total` components fp32 -> half (round to nearest even, subnormals kept, beyond the range +-inf) and back (exact)
+void launch_flat16_encode(const float* x, int64_t total, void* halves, hipStream_t s);
+void launch_flat16_decode(const void* halves, int64_t total, float* out, hipStream_t s);
 
 // IVF scalar quantizer (IndexIVFScalarQuantizer::search, IndexScalarQuantizer.cpp:884-989; scan_sq.hip): a.codes holds the lists'
 // codes as rows of sq_code_size(d, qtype) bytes; a.queries, a.coarse (the centroids: the L2 residual of every probe), a.keys,

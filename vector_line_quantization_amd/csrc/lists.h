@@ -16,9 +16,10 @@ int lists_init(ListStore& ls, int64_t nlist, int code_size, int side_size, hipSt
 // Replace the lists by packed ones: offsets [nlist+1] (host or device memory; checked by check_list_offsets, list_offsets.h,
 // with `noun` and `len_limit`), codes / ids [offsets[nlist]] rows, side likewise or nullptr (the side field is then left
 // unwritten).  Synchronises s before the arrays are re-reserved -- that frees blocks the stream may still be reading -- and
-// again at the end.  *ntotal = offsets[nlist] once the offsets have passed.
+// again at the end.  *ntotal = offsets[nlist] once the offsets have passed.  codes_by_caller: `codes` is the caller's source
+// in another format (only looked at for null); ls.codes is sized and left for the caller's encoder to fill.
 int lists_load(ListStore& ls, const void* codes, const void* side, const int64_t* ids, const int64_t* offsets, const char* noun,
-               int64_t len_limit, hipStream_t s, int64_t* ntotal);
+               int64_t len_limit, hipStream_t s, int64_t* ntotal, bool codes_by_caller = false);
 // every list empty, no capacity left behind (the next add lays the lists out afresh); synchronises
 int lists_clear(ListStore& ls, hipStream_t s);
 // the readers of list i (0 <= i < nlist, the caller's check) behind everything queued on s; null outputs are skipped

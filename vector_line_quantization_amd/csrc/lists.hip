@@ -159,7 +159,7 @@ int lists_clear(ListStore& ls, hipStream_t s) {
 }
 
 int lists_load(ListStore& ls, const void* codes, const void* side, const int64_t* ids, const int64_t* offsets, const char* noun,
-               int64_t len_limit, hipStream_t s, int64_t* ntotal) {
+               int64_t len_limit, hipStream_t s, int64_t* ntotal, bool codes_by_caller) {
     const size_t nlist = (size_t)ls.nlist;
     std::vector<int64_t> off(nlist + 1), len(nlist);
     HIP_TRY(hipMemcpy(off.data(), offsets, off.size() * 8, hipMemcpyDefault));
@@ -174,7 +174,7 @@ int lists_load(ListStore& ls, const void* codes, const void* side, const int64_t
     if (ls.side_size) TRY(ls.side.reserve((size_t)nt * ls.side_size + 16));
     TRY(ls.ids.reserve((size_t)nt * 8 + 16));
     if (nt > 0) {
-        HIP_TRY(hipMemcpyAsync(ls.codes.p, codes, (size_t)nt * ls.code_size, hipMemcpyDefault, s));
+        if (!codes_by_caller) HIP_TRY(hipMemcpyAsync(ls.codes.p, codes, (size_t)nt * ls.code_size, hipMemcpyDefault, s));
         if (ls.side_size && side) HIP_TRY(hipMemcpyAsync(ls.side.p, side, (size_t)nt * ls.side_size, hipMemcpyDefault, s));
         HIP_TRY(hipMemcpyAsync(ls.ids.p, ids, (size_t)nt * 8, hipMemcpyDefault, s));
     }

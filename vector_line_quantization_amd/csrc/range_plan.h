@@ -34,12 +34,12 @@ inline RangeLayout range_layout(int nprobe, int d) {
     return l;
 }
 
-inline RangePlan plan_flat_range(int d, int nprobe) {
+inline RangePlan plan_flat_range(int d, int nprobe, int storage = kFlatStoreF32) {
     RangePlan p;
     if (d < 1 || nprobe < 1 || nprobe > kFlatMaxProbes) return p;
     p.lay = range_layout(nprobe, d);
     if (p.lay.bytes > kFlatLdsLimit) return p;
-    p.read = d % 4 == 0 ? kFlatReadTile128 : kFlatReadDword;
+    p.read = flat_read_path(d, storage);
     p.ok = true;
     return p;
 }

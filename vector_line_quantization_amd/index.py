@@ -460,17 +460,25 @@ class _GpuIVF:
 class GpuIVFFlat(_GpuIVF):
     """faiss::IndexIVFFlat / gpu::GpuIndexIVFFlat (IndexIVF.h:132-205, gpu/GpuIndexIVFFlat.h): inverted lists of the vectors
     themselves, exact distances.  metric "l2": ascending squared distances, FLT_MAX / -1 padding; "ip": descending inner
-    products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfflat_*)."""
+    products, -FLT_MAX / -1 padding (include/vlq_ivfpq.h, vlq_ivfflat_*).
+    storage "f16" (GpuIndexIVFFlatConfig::useFloat16IVFStorage): the lists hold half(x), half the bytes to keep and to scan; all
+    arithmetic stays fp32, inputs and outputs stay float32, and the results are bit for bit those of an "f32" index over
+    x.astype(float16).astype(float32).  GpuRefineFlat over such an index re-ranks its shortlist against the unrounded vectors:
+    a compressed first stage with an exact second one."""
 
     _KIND = "vlq_ivfflat_"
+    STORAGES = {"f32": 0, "f16": 1}
 
-    def __init__(self, d, nlist, device=0, metric="l2"):
+    def __init__(self, d, nlist, device=0, metric="l2", storage="f32"):
         self.d, self.nlist, self.device = d, nlist, device
         self._h = C.c_void_p()
         if metric not in self.METRICS:
             raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
-        self.metric = metric
-        check(lib().vlq_ivfflat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist), C.c_int(self.METRICS[metric])))
+        if storage not in self.STORAGES:
+            raise ValueError("storage %r (one of 'f32', 'f16')" % (storage,))
+        self.metric, self.storage = metric, storage
+        check(lib().vlq_ivfflat_create_ex(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(nlist), C.c_int(self.METRICS[metric]),
+                                          C.c_int(self.STORAGES[storage])))
 
     def set_lists(self, vecs, ids, list_offsets):
         """vecs [ntotal][d] float32 and ids [ntotal] in list-contiguous order, list_offsets [nlist + 1]"""
