@@ -668,11 +668,25 @@ int vlq_sq_last_scan_info(vlq_sq_t h, char* buf, int cap);
  * d >= 1 on the GEMM path; the small-batch path holds one query in LDS (d up to about 30 000: VLQ_ERR_UNSUPPORTED beyond).
  * range_search is IndexFlat::range_search (IndexFlat.cpp:58-70; utils.cpp:1090-1262) under the same dispatch and with the same
  * distances bit for bit; see vlq_flat_range_search below.
- * Not built: remove_ids, float16 storage.  Pointers [h|d]. */
+ * float16 storage (GpuIndexFlatConfig::useFloat16; vlq_flat_create_ex with storage = 1; csrc/scan_knn16.hip,
+ * csrc/refine_flat16.hip): the rows are half(x), round to nearest even (half subnormals kept, values beyond the half range
+ * become +-inf: numpy's astype(float16)), 2 * d bytes per vector.  The query stays fp32 and every operation is fp32 in the
+ * order the fp32 handle uses for the same call -- the n < 20 && d % 4 == 0 dispatch, the per-pair SSE order below it, the
+ * fmaf chain with the (|x|^2 + |y|^2) - 2 ip epilogue above it, |y|^2 of the widened row in fvec_norm_L2sqr's order, the
+ * total order (distance, position), the padding -- so the handle returns, bit for bit, what an fp32 handle holding
+ * float(half(x)) returns from search, refine and compute_distance_subset (their bad-label flag included).  reconstruct_n
+ * returns the widened stored bits.  Every entry point keeps fp32 at the boundary.  The last-scan and last-refine texts of such
+ * a handle name the f16 kernel and end in " store=f16 read=tile128" (d % 8 == 0) or " store=f16 read=row".
+ * Not built: remove_ids, range search over float16 storage (VLQ_ERR_UNSUPPORTED), half inputs or outputs.
+ * Pointers [h|d]. */
 typedef struct vlq_flat_s* vlq_flat_t;
 
 /* metric: 0 = inner product, 1 = L2 (MetricType of Index.h); any other value: VLQ_ERR_INVALID */
 int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric);
+/* the same with the rows' storage: 0 = float32 (what vlq_flat_create makes), 1 = float16; anything else VLQ_ERR_INVALID */
+int vlq_flat_create_ex(vlq_flat_t* out, int device, int d, int metric, int storage);
+/* the storage the handle was created with (-1: null handle) */
+int vlq_flat_storage(vlq_flat_t h);
 void vlq_flat_destroy(vlq_flat_t h);
 int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream);
 /* IndexFlat::add (IndexFlat.cpp:24-28): x[n*d] [h|d] appended in input order; label of a vector = its position.

@@ -44,7 +44,7 @@ SYMBOLS = [
     "vlq_sq_set_codes", "vlq_sq_add", "vlq_sq_encode", "vlq_sq_get_codes", "vlq_sq_reconstruct", "vlq_sq_ntotal", "vlq_sq_reset",
     "vlq_sq_reserve_memory", "vlq_sq_search", "vlq_sq_set_scan_split", "vlq_sq_last_scan_info",
     # flat exact k-NN (vlq_flat_t)
-    "vlq_flat_create", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
+    "vlq_flat_create", "vlq_flat_create_ex", "vlq_flat_storage", "vlq_flat_destroy", "vlq_flat_set_stream", "vlq_flat_add", "vlq_flat_ntotal", "vlq_flat_reset",
     "vlq_flat_reserve_memory", "vlq_flat_reconstruct_n", "vlq_flat_search", "vlq_flat_set_scan_split", "vlq_flat_last_scan_info",
     "vlq_flat_compute_distance_subset", "vlq_flat_refine", "vlq_flat_last_refine_info", "vlq_flat_range_search", "vlq_flat_range_result",
     # LSH: sign-bit codes and Hamming k-NN (vlq_lsh_t)

@@ -417,6 +417,12 @@ struct KnnArgs {
     bool ip;
 };
 bool launch_knn(const KnnArgs& a, const KnnPlan& P, hipStream_t s);
+// The same search over float16 rows (vlq_flat_create_ex with storage = 1; scan_knn16.hip): a.xb points at rows of a.d HALVES,
+// P is plan_knn's with kFlatStoreF16, everything else is as above and the arithmetic is fp32, so the rows are those of
+// launch_knn over float(half(x)) bit for bit.  widen: P.chunk x d floats, the GEMM matrix route's widened chunk (else unused).
+bool launch_knn16(const KnnArgs& a, const KnnPlan& P, float* widen, hipStream_t s);
+// launch_row_norms over n rows of d halves: the widened row in fvec_norm_L2sqr's order
+void launch_row_norms16(const void* halves, int64_t n, int d, float* out, hipStream_t s);
 
 // Range search of the flat index (faiss::IndexFlat::range_search, IndexFlat.cpp:58-70, utils.cpp:1090-1262; scan_range_knn.hip),
 // one of its two passes over one page (nq <= P.page) of queries xq [nq][d]; plan_knn_range (knn_range_plan.h) decides for the
@@ -544,5 +550,7 @@ struct RefineFlatArgs {
     bool ip;
 };
 bool launch_refine_flat(const RefineFlatArgs& a, const RefineFlatPlan& P, bool select, hipStream_t s);
+// the same over a float16 store (refine_flat16.hip): a.xb points at rows of a.d HALVES, P is plan_refine_flat's with kFlatStoreF16
+bool launch_refine_flat16(const RefineFlatArgs& a, const RefineFlatPlan& P, bool select, hipStream_t s);
 
 }  // namespace vlq

@@ -4,6 +4,10 @@
 // IndexFlat's own: the squared norms in a buffer that grows with the list (launch_row_norms over the appended rows only), the
 // call's plan and the scan of one page under it (scan_knn.hip, knn_plan.h), the two passes of range_search and the hits it
 // leaves in the handle (scan_range_knn.hip, knn_range_plan.h), and IndexRefineFlat's seam (refine_flat.hip).
+// Float16 storage (vlq_flat_create_ex, GpuIndexFlatConfig::useFloat16): the rows are 2 * d bytes of half(x).  add encodes the
+// staged batch into a workspace and appends; reconstruct_n decodes; search, refine and compute_distance_subset go to
+// scan_knn16.hip / refine_flat16.hip under the same plans with kFlatStoreF16; the norms are those of the widened rows.  fp32
+// stays at every boundary.  range_search is refused.
 #include "knn_plan.h"
 #include "knn_range_plan.h"
 #include "one_list.h"
@@ -12,6 +16,8 @@
 struct vlq_flat_s : OneListShell {      // (force_tile: the row tile)
     int d = 0;
     int metric = 1;               // MetricType (Index.h): 0 = inner product, 1 = L2
+    int storage = vlq::kFlatStoreF32;     // FlatStore (flat_plan.h): what a stored component is
+    DevBuf ws_half, ws_widen;     // f16: the encoded batch of an add; the widened chunk of the GEMM matrix route / rows of reconstruct_n
     DevBuf norms;                 // [capacity] |y|^2 in fvec_norm_L2sqr's order
     DevBuf ws_qn, ws_matrix, ws_zero;
     size_t zero_floats = 0;       // floats of ws_zero known to be zero
@@ -44,7 +50,8 @@ int flat_plan_fail(vlq_flat_t h, int64_t n, int k, const vlq::KnnPlan& P) {
 int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float* xd, int k, float* Dd, int64_t* Id) {
     const bool ip = h->metric == 0;
     vlq::KnnArgs a = {};
-    a.xb = h->lists.codes.as<float>();
+    const bool f16 = h->storage == vlq::kFlatStoreF16;
+    a.xb = h->lists.codes.as<float>();       // (f16: rows of d halves, read by scan_knn16.hip)
     a.yn = h->norms.as<float>();
     a.xq = xd;
     a.D = Dd; a.I = Id;
@@ -59,6 +66,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
     } else {
         TRY(h->ws_part.reserve((size_t)n * (P.S + 1) * k * 8));
         TRY(h->ws_matrix.reserve((size_t)n * (size_t)P.chunk * 4 + 16));
+        if (f16 && P.path == vlq::kKnnGemm) TRY(h->ws_widen.reserve((size_t)P.chunk * h->d * 4 + 16));
         if (ip && P.path == vlq::kKnnGemm) {
             const size_t nz = (size_t)std::max<int64_t>(n, P.chunk);
             if (nz > h->zero_floats) {
@@ -71,7 +79,8 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
     }
     a.part = h->ws_part.as<unsigned long long>();
     a.matrix = h->ws_matrix.as<float>();
-    if (!vlq::launch_knn(a, P, h->ctx.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat search: no kernel for rows=%d kpl=%d (%s / %s)", P.rows, P.kpl,
+    const bool built = f16 ? vlq::launch_knn16(a, P, h->ws_widen.as<float>(), h->ctx.stream) : vlq::launch_knn(a, P, h->ctx.stream);
+    if (!built) return fail(VLQ_ERR_UNSUPPORTED, "flat search: no kernel for rows=%d kpl=%d (%s / %s)", P.rows, P.kpl,
                                                         vlq::knn_path_name(P.path), vlq::knn_route_name(P.route));
     HIP_TRY(hipGetLastError());
     return VLQ_OK;
@@ -81,6 +90,7 @@ int flat_search_page(vlq_flat_t h, const vlq::KnnPlan& P, int64_t n, const float
 // flag is read behind every call (one stream synchronisation): the reference asserts there (IndexFlat.cpp:240-242).
 int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int64_t n, const float* xd, const int64_t* ld, int k_base,
                     const float* bd, int k, float* Dd, int64_t* Id) {
+    const bool f16 = h->storage == vlq::kFlatStoreF16;
     TRY(h->refine_bad.reserve(16));
     HIP_TRY(hipMemsetAsync(h->refine_bad.p, 0, 4, h->ctx.stream));
     for (int64_t i0 = 0; i0 < n; i0 += P.page) {
@@ -93,11 +103,13 @@ int refine_flat_dev(vlq_flat_t h, const vlq::RefineFlatPlan& P, bool select, int
         a.I = Id ? Id + i0 * k : nullptr;
         a.bad = h->refine_bad.as<int>();
         a.nq = std::min(P.page, n - i0); a.ntotal = h->ntotal; a.d = h->d; a.k_base = k_base; a.k = k; a.ip = h->metric == 0;
-        if (!vlq::launch_refine_flat(a, P, select, h->ctx.stream)) return fail(VLQ_ERR_UNSUPPORTED, "flat refine: no kernel for this plan");
+        const bool built = f16 ? vlq::launch_refine_flat16(a, P, select, h->ctx.stream) : vlq::launch_refine_flat(a, P, select, h->ctx.stream);
+        if (!built) return fail(VLQ_ERR_UNSUPPORTED, "flat refine: no kernel for this plan");
         HIP_TRY(hipGetLastError());
     }
-    snprintf(h->last_refine, sizeof(h->last_refine), "kernel=refine_flat_kernel select=%d metric=%s read=%s waves=%d trips=%d slots=%d page=%lld lds=%zu",
-             select ? 1 : 0, h->metric == 0 ? "ip" : "l2", vlq::flat_read_name(P.read), P.waves, P.trips, P.slots, (long long)P.page, P.lds);
+    snprintf(h->last_refine, sizeof(h->last_refine), "kernel=%s select=%d metric=%s read=%s waves=%d trips=%d slots=%d page=%lld lds=%zu%s",
+             f16 ? "refine_flat16_kernel" : "refine_flat_kernel", select ? 1 : 0, h->metric == 0 ? "ip" : "l2", vlq::flat_read_name(P.read), P.waves,
+             P.trips, P.slots, (long long)P.page, P.lds, f16 ? " store=f16" : "");
     return VLQ_OK;
 }
 
@@ -185,16 +197,19 @@ int flat_range_dev(vlq_flat_t h, const vlq::KnnRangePlan& P, int64_t n, const fl
 
 extern "C" {
 
-int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric) {
+int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric) { return vlq_flat_create_ex(out, device, d, metric, vlq::kFlatStoreF32); }
+
+int vlq_flat_create_ex(vlq_flat_t* out, int device, int d, int metric, int storage) {
     if (!out) return fail(VLQ_ERR_INVALID, "null out");
     *out = nullptr;
+    if (storage != vlq::kFlatStoreF32 && storage != vlq::kFlatStoreF16) return fail(VLQ_ERR_INVALID, "storage %d (0 = float32, 1 = float16)", storage);
     if (d <= 0) return fail(VLQ_ERR_INVALID, "d=%d must be positive", d);
     if (d > (1 << 26)) return fail(VLQ_ERR_UNSUPPORTED, "d=%d: rows beyond 2^28 bytes", d);
     if (metric != 0 && metric != 1) return fail(VLQ_ERR_INVALID, "metric %d (0 = inner product, 1 = L2: MetricType of Index.h)", metric);
     vlq_flat_s* h = new (std::nothrow) vlq_flat_s();
     if (!h) return fail(VLQ_ERR_INVALID, "out of memory");
-    h->d = d; h->metric = metric;
-    int rc = one_open(h, device, 4 * d);
+    h->d = d; h->metric = metric; h->storage = storage;
+    int rc = one_open(h, device, vlq::flat_code_size(d, storage));
     if (rc == VLQ_OK) rc = h->ws_matrix.reserve(16);
     if (rc == VLQ_OK) rc = h->norms.reserve(16);
     if (rc != VLQ_OK) { vlq_flat_destroy(h); return rc; }
@@ -203,6 +218,7 @@ int vlq_flat_create(vlq_flat_t* out, int device, int d, int metric) {
 }
 
 void vlq_flat_destroy(vlq_flat_t h) { one_destroy(h); }
+int vlq_flat_storage(vlq_flat_t h) { return h ? h->storage : -1; }
 int vlq_flat_set_stream(vlq_flat_t h, void* hip_stream) { return one_set_stream(h, hip_stream); }
 
 // IndexFlat::add (IndexFlat.cpp:24-28): appended in input order; only the new rows' norms are computed
@@ -218,6 +234,15 @@ int vlq_flat_add(vlq_flat_t h, int64_t n, const float* x) {
     TRY(one_route(h, n));
     TRY(norms_reserve(h, h->ntotal + n));
     const int64_t n0 = h->ntotal;
+    if (h->storage == vlq::kFlatStoreF16) {     // half(x) of the batch, then the norms of the stored (widened) rows
+        TRY(h->ws_half.reserve((size_t)n * h->d * 2 + 16));
+        vlq::launch_flat16_encode((const float*)xd, n * h->d, h->ws_half.p, h->ctx.stream);
+        HIP_TRY(hipGetLastError());
+        TRY(one_append(h, n, h->ws_half.as<uint8_t>()));
+        vlq::launch_row_norms16(h->lists.codes.as<uint8_t>() + (size_t)n0 * h->d * 2, h->ntotal - n0, h->d, h->norms.as<float>() + n0, h->ctx.stream);
+        HIP_TRY(hipGetLastError());
+        return VLQ_OK;
+    }
     TRY(one_append(h, n, (const uint8_t*)xd));
     // (the one list starts at 0: the new rows sit behind the stored ones)
     vlq::launch_row_norms(h->lists.codes.as<float>() + (size_t)n0 * h->d, h->ntotal - n0, h->d, h->norms.as<float>() + n0, h->ctx.stream);
@@ -244,7 +269,28 @@ int vlq_flat_reconstruct_n(vlq_flat_t h, int64_t i0, int64_t n, float* out) {
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (n < 0 || (n > 0 && (i0 < 0 || i0 + n > h->ntotal)))
         return fail(VLQ_ERR_INVALID, "vectors %lld .. %lld outside 0 .. ntotal=%lld", (long long)i0, (long long)(i0 + n), (long long)h->ntotal);
-    return one_get_rows(h, i0, n, out);
+    if (h->storage != vlq::kFlatStoreF16) return one_get_rows(h, i0, n, out);
+    if (n == 0) return VLQ_OK;
+    if (!out) return fail(VLQ_ERR_INVALID, "null out");
+    // the widened stored bits: straight into a device `out`, through a bounded workspace in pages of rows otherwise
+    TRY(set_dev(&h->ctx));
+    const uint8_t* rows = h->lists.codes.as<uint8_t>();
+    const size_t d = (size_t)h->d;
+    if (is_device_ptr(out)) {
+        vlq::launch_flat16_decode(rows + (size_t)i0 * d * 2, n * h->d, out, h->ctx.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->ctx.stream));
+        return VLQ_OK;
+    }
+    const int64_t page = std::max<int64_t>(1, (int64_t)((size_t(64) << 20) / (d * 4)));
+    TRY(h->ws_widen.reserve((size_t)std::min(page, n) * d * 4 + 16));
+    for (int64_t r0 = 0; r0 < n; r0 += page) {
+        const int64_t nr = std::min(page, n - r0);
+        vlq::launch_flat16_decode(rows + (size_t)(i0 + r0) * d * 2, nr * h->d, h->ws_widen.as<float>(), h->ctx.stream);
+        HIP_TRY(hipGetLastError());
+        TRY(one_fetch(&h->ctx, out + (size_t)r0 * d, h->ws_widen.p, (size_t)nr * d * 4));
+    }
+    return VLQ_OK;
 }
 
 // IndexFlat::search (IndexFlat.cpp:41-56)
@@ -254,16 +300,19 @@ int vlq_flat_search(vlq_flat_t h, int64_t n, const float* x, int k, float* D, in
     TRY(one_search_args(n, x, k, D, I));
     if (n == 0) return VLQ_OK;
     // the dispatch and the plan are the call's: a last short page takes the path of the first (utils.cpp:741, :939)
-    const vlq::KnnPlan P = vlq::plan_knn(n, h->ntotal, h->d, k, h->force_tile, h->force_s);
+    const vlq::KnnPlan P = vlq::plan_knn(n, h->ntotal, h->d, k, h->force_tile, h->force_s, h->storage);
+    const bool f16 = h->storage == vlq::kFlatStoreF16;
     if (!P.ok) return flat_plan_fail(h, n, k, P);
     return one_search(
         h, n, x, (size_t)h->d * 4, k, D, I, P.page,
         [&](int64_t ni, const void* xd, float* Dd, int64_t* Id) { return flat_search_page(h, P, ni, (const float*)xd, k, Dd, Id); },
         [&] {
-            snprintf(h->last_scan, sizeof(h->last_scan), "path=%s route=%s kernel=%s rows=%d S=%d slice=%lld chunk=%lld page=%lld lds=%zu join=%d",
-                     vlq::knn_path_name(P.path), vlq::knn_route_name(P.route),
-                     P.route == vlq::kKnnFused ? "knn_gemm_kernel" : P.path == vlq::kKnnDirect ? "knn_direct_kernel" : "coarse_dist+knn_select_kernel",
-                     P.rows, P.S, (long long)P.slice_len, (long long)P.chunk, (long long)P.page, P.lds, P.join ? 1 : 0);
+            const char* kernel = P.route == vlq::kKnnFused ? (f16 ? "knn_gemm16_kernel" : "knn_gemm_kernel")
+                                 : P.path == vlq::kKnnDirect ? (f16 ? "knn_direct16_kernel" : "knn_direct_kernel")
+                                 : (f16 ? "flat16_decode+coarse_dist+knn_select_kernel" : "coarse_dist+knn_select_kernel");
+            snprintf(h->last_scan, sizeof(h->last_scan), "path=%s route=%s kernel=%s rows=%d S=%d slice=%lld chunk=%lld page=%lld lds=%zu join=%d%s%s",
+                     vlq::knn_path_name(P.path), vlq::knn_route_name(P.route), kernel, P.rows, P.S, (long long)P.slice_len, (long long)P.chunk,
+                     (long long)P.page, P.lds, P.join ? 1 : 0, f16 ? " store=f16 read=" : "", f16 ? vlq::flat_read_name(P.read) : "");
         });
 }
 
@@ -274,6 +323,8 @@ int vlq_flat_range_search(vlq_flat_t h, int64_t n, const float* x, float radius,
     TRY(set_dev(&h->ctx));
     h->range.drop();
     if (total) *total = 0;
+    if (h->storage == vlq::kFlatStoreF16)
+        return fail(VLQ_ERR_UNSUPPORTED, "range search over float16 storage is not built (DESIGN.md section 7); use a float32 index");
     if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
     if (!lims || (n > 0 && !x)) return fail(VLQ_ERR_INVALID, "null buffer");
     hipStream_t s = h->ctx.stream;
@@ -319,7 +370,7 @@ int vlq_flat_compute_distance_subset(vlq_flat_t h, int64_t n, const float* x, in
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
     if (n > 0 && (!x || !distances || !labels)) return fail(VLQ_ERR_INVALID, "null buffer");
-    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k, k, false);
+    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k, k, false, h->storage);
     if (!P.ok) return refine_flat_plan_fail(h, k, k, P);
     if (n == 0) return VLQ_OK;
     TRY(set_dev(&h->ctx));
@@ -338,7 +389,7 @@ int vlq_flat_refine(vlq_flat_t h, int64_t n, const float* x, int k_base, const f
     if (!h) return fail(VLQ_ERR_INVALID, "null handle");
     if (n < 0) return fail(VLQ_ERR_INVALID, "n=%lld < 0", (long long)n);
     if (n > 0 && (!x || !base_D || !base_I || !D || !I)) return fail(VLQ_ERR_INVALID, "null buffer");
-    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k_base, k, true);
+    const vlq::RefineFlatPlan P = vlq::plan_refine_flat(h->d, k_base, k, true, h->storage);
     if (!P.ok) return refine_flat_plan_fail(h, k_base, k, P);
     if (k != k_base && ((const void*)D == (const void*)base_D || (const void*)I == (const void*)base_I))
         return fail(VLQ_ERR_INVALID, "D / I may be base_D / base_I only when k == k_base");

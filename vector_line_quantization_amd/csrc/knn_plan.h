@@ -13,9 +13,16 @@
 //               a bounded scratch matrix, `S` waves per query select their slice of it, and a join folds the S parts and the
 //               running row [page][S + 1][k] into the running row (the final rows after the last chunk).
 // Scratch never holds a term in nq x ntotal: the queries are paged and the chunk is cut to the matrix cap.
+//
+// Storage (flat_plan.h: FlatStore).  kFlatStoreF16: the rows are half(x) and scan_knn16.hip reads them.  Dispatch, routes, row
+// tiles, slices and pages are those of fp32; what differs is the read path (`read`: tile128 iff d % 8 == 0), the direct kernel's
+// LDS (its row path needs no row tiles) and the chunk of the GEMM matrix route, whose rows are widened into an fp32 workspace
+// [chunk][d] that shares the matrix' budget: pg x chunk + chunk x d floats stay within kKnnMatrixLimit.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "flat_plan.h"      // FlatStore, flat_read_path
 
 namespace vlq {
 
@@ -54,7 +61,8 @@ struct KnnPlan {
     int64_t page = 0;       // queries per launch
     size_t lds = 0;         // dynamic LDS of the scan kernel (fused: knn_gemm_kernel, direct: knn_direct_kernel; GEMM matrix: 0, the
                             // coarse distance kernel's own)
-    size_t scratch = 0;     // bytes of scratch of a page: matrix + partial rows + norms / zeros
+    size_t scratch = 0;     // bytes of scratch of a page: matrix + partial rows + norms / zeros (+ the widened chunk, float16 storage)
+    int read = kFlatReadTile128;    // float16 storage: how scan_knn16.hip reads a stored row (tile128 or row)
 };
 
 // knn_gemm_kernel: the staged tiles (later the distance tile [rows][kKnnColTile + 1]) at 0, then the rows' best keys
@@ -65,11 +73,17 @@ inline size_t knn_fused_lds(int rows, int kpl) {
 }
 // knn_direct_kernel: the queries [rows][d], then the four waves' row tiles
 inline size_t knn_direct_lds(int rows, int d) { return ((size_t)rows * d * 4 + 15) / 16 * 16 + kKnnDirectTileBytes; }
+// knn_direct16_kernel: the same; its row path (d % 8 != 0) turns nothing through LDS
+inline size_t knn_direct_lds(int rows, int d, int storage) {
+    return knn_direct_lds(rows, d) - ((storage == kFlatStoreF16 && d % 8 != 0) ? kKnnDirectTileBytes : 0);
+}
 
 // nq_call: the queries of the whole call (the dispatch); force_rows / force_s: vlq_flat_set_scan_split (0 = the plan decides;
 // a forced row tile that does not fit LDS at this k shrinks, forced slices never cut below one column tile)
-inline KnnPlan plan_knn(int64_t nq_call, int64_t ntotal, int d, int k, int force_rows = 0, int force_s = 0) {
+inline KnnPlan plan_knn(int64_t nq_call, int64_t ntotal, int d, int k, int force_rows = 0, int force_s = 0, int storage = kFlatStoreF32) {
     KnnPlan p;
+    const bool f16 = storage == kFlatStoreF16;
+    if (f16) p.read = flat_read_path(d, storage);
     if (nq_call < 1 || d < 1) { p.why = "nq and d must be positive"; return p; }
     if (ntotal < 0 || ntotal >= (int64_t(1) << 32)) { p.why = "ntotal beyond the key's 32-bit position"; return p; }
     if (k < 1 || k > kKnnMaxK) { p.why = "k outside 1..1024"; return p; }
@@ -120,9 +134,9 @@ inline KnnPlan plan_knn(int64_t nq_call, int64_t ntotal, int d, int k, int force
     // matrix route
     if (p.path == kKnnDirect) {
         int rows = nq_call <= 1 ? 1 : nq_call <= 4 ? 4 : kKnnDirectBelow - 1;      // the direct kernel's instantiations
-        while (rows > 1 && knn_direct_lds(rows, d) > kKnnLdsLimit) rows = rows > 4 ? 4 : 1;
+        while (rows > 1 && knn_direct_lds(rows, d, storage) > kKnnLdsLimit) rows = rows > 4 ? 4 : 1;
         p.rows = rows;
-        p.lds = knn_direct_lds(rows, d);
+        p.lds = knn_direct_lds(rows, d, storage);
         if (p.lds > kKnnLdsLimit) { p.why = "one query of this d does not fit 160 KB of LDS beside the row tiles"; return p; }
         p.page = kKnnDirectBelow - 1;
     } else {
@@ -131,9 +145,11 @@ inline KnnPlan plan_knn(int64_t nq_call, int64_t ntotal, int d, int k, int force
         p.page = kKnnMatrixPage;
     }
     int64_t pg = p.page < page0 ? p.page : page0;
-    int64_t chunk = (int64_t)(kKnnMatrixLimit / 4) / pg;
+    const bool widen = f16 && p.path == kKnnGemm;      // the chunk's rows as fp32 beside the matrix, within its budget
+    int64_t chunk = (int64_t)(kKnnMatrixLimit / 4) / (widen ? pg + d : pg);
     if (chunk > kKnnMaxChunk) chunk = kKnnMaxChunk;
     chunk = chunk / kKnnColTile * kKnnColTile;
+    if (chunk < kKnnColTile) { p.why = "one column tile of this d, widened to fp32, does not fit the matrix budget"; return p; }
     if (chunk > ntotal) chunk = ntotal;
     p.chunk = chunk;
     int64_t S = force_s;
@@ -154,7 +170,7 @@ inline KnnPlan plan_knn(int64_t nq_call, int64_t ntotal, int d, int k, int force
     if (pg > by_part) { pg = by_part; p.page = pg; }
     // matrix [pg][chunk], parts and the running row [pg][S + 1][k], the queries' norms, zero norms of a chunk (inner product)
     p.scratch = (size_t)pg * (size_t)chunk * 4 + (size_t)pg * (S + 1) * k * 8 + (size_t)pg * 4 +
-                (size_t)(chunk > pg ? chunk : pg) * 4;
+                (size_t)(chunk > pg ? chunk : pg) * 4 + (widen ? (size_t)chunk * d * 4 : 0);
     if (p.scratch > kKnnScratchLimit) { p.why = "scratch beyond 256 MB"; return p; }
     p.ok = true;
     return p;

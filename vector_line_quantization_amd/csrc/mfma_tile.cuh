@@ -62,6 +62,57 @@ struct MfmaTile {
         }
     }
 
+    // The same two steps over rows kept as float16 (scan_knn16.hip: the stored vectors of an f16 flat index).  A thread's unit is
+    // eight halves -- one dwordx4 -- so a step of KC halves takes half the load instructions and half the prefetch registers of
+    // Frag<N>.  vec: 8 = rows are 16-byte aligned (d % 8 == 0), 4 = 8-byte aligned (d % 4 == 0: two 8-byte loads), otherwise
+    // 2-byte loads.  Zeros behind lim and behind d, as fetch does (a zero half widens to 0.f).  commit16 widens (exact) and
+    // writes the very layout commit writes, [2 parity][N][S] fp32: multiply() and everything behind it do not know the storage.
+    typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+    template <int N>
+    struct Frag16 { half8 v[N * (KC / 8) / 256]; };
+    template <int N>
+    static __device__ __forceinline__ void fetch16(const _Float16* __restrict__ x, int64_t n0, int64_t lim, int d, int k0, int vec,
+                                                   Frag16<N>& fr, int t) {
+        static_assert(N * (KC / 8) % 256 == 0, "whole trips of the 256 threads");
+#pragma unroll
+        for (int i = 0; i < N * (KC / 8) / 256; i++) {
+            const int f = t + i * 256;
+            const int row = f / (KC / 8), v = f % (KC / 8);
+            const int kk = k0 + 8 * v;
+            const int64_t grow = n0 + row;
+            half8 val = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (grow < lim && kk < d) {
+                const _Float16* p = x + grow * d + kk;
+                if (vec == 8) {                             // (d % 8 == 0: kk < d is kk + 8 <= d)
+                    val = *reinterpret_cast<const half8*>(p);
+                } else if (vec == 4) {                      // (d % 4 == 0: kk < d is kk + 4 <= d)
+                    const half4 lo = *reinterpret_cast<const half4*>(p);
+                    half4 hi = {0, 0, 0, 0};
+                    if (kk + 8 <= d) hi = *reinterpret_cast<const half4*>(p + 4);
+                    val = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                        if (kk + e < d) val[e] = p[e];
+                }
+            }
+            fr.v[i] = val;
+        }
+    }
+    template <int N>
+    static __device__ __forceinline__ void commit16(const Frag16<N>& fr, float* dst, int t) {
+        static_assert(S % 4 == 0, "16-byte stores");
+#pragma unroll
+        for (int i = 0; i < N * (KC / 8) / 256; i++) {
+            const int f = t + i * 256;
+            const int row = f / (KC / 8), v = f % (KC / 8);
+            const half8 h = fr.v[i];
+            *reinterpret_cast<float4*>(dst + (0 * N + row) * S + 4 * v) = make_float4((float)h[0], (float)h[2], (float)h[4], (float)h[6]);
+            *reinterpret_cast<float4*>(dst + (1 * N + row) * S + 4 * v) = make_float4((float)h[1], (float)h[3], (float)h[5], (float)h[7]);
+        }
+    }
+
     static __device__ __forceinline__ float* lds_a(float* sm) { return sm; }
     static __device__ __forceinline__ float* lds_b(float* sm) { return sm + 2 * ROWS * S; }
 

@@ -29,7 +29,8 @@ struct RefineFlatPlan {
     bool ok = false;
     int err = 0;            // !ok: 1 = an argument outside its range (VLQ_ERR_INVALID), 2 = the shape is not built (VLQ_ERR_UNSUPPORTED)
     const char* why = "";
-    int read = kFlatReadTile128;    // d % 4 == 0: gathered 64 x 128 B tiles; otherwise the per-lane dword walk
+    int read = kFlatReadTile128;    // d % 4 == 0: gathered 64 x 128 B tiles; otherwise the per-lane dword walk (float16 rows,
+                                    // refine_flat16.hip: d % 8 == 0, otherwise the per-lane walk over halves; the layout is the same)
     int trips = 0;          // trips of 64 candidates
     int slots = 0;          // keys sorted: a power of two, 64 .. 1024
     int waves = 0;          // 1, 2 or 4: one per trip up to four
@@ -49,13 +50,13 @@ inline RefineFlatLayout refine_flat_layout(int waves, int slots, int d, bool sel
 }
 
 // select = false: compute_distance_subset (k = k_base, no keys and no labels in LDS)
-inline RefineFlatPlan plan_refine_flat(int d, int k_base, int k, bool select = true) {
+inline RefineFlatPlan plan_refine_flat(int d, int k_base, int k, bool select = true, int storage = kFlatStoreF32) {
     RefineFlatPlan p;
     p.err = 1;
     if (d < 1) { p.why = "d must be positive"; return p; }
     if (k_base < 1 || k_base > kRefineFlatMaxK) { p.why = "k_base outside 1..1024"; return p; }
     if (k < 1 || k > k_base) { p.why = "k outside 1..k_base"; return p; }
-    p.read = d % 4 == 0 ? kFlatReadTile128 : kFlatReadDword;
+    p.read = flat_read_path(d, storage);
     p.trips = (k_base + kRefineFlatTrip - 1) / kRefineFlatTrip;
     p.slots = kRefineFlatTrip;
     while (p.slots < k_base) p.slots <<= 1;

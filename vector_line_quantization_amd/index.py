@@ -864,18 +864,25 @@ class GpuFlat(_GpuOneList):
     """faiss::IndexFlat / IndexFlatL2 / IndexFlatIP (gpu::GpuIndexFlat): the exact brute-force index.  metric "l2": ascending
     squared distances, FLT_MAX / -1 padding; "ip": descending inner products, -FLT_MAX / -1 padding.  Labels are positions in
     the order of add.  Fewer than 20 queries with d % 4 == 0 take the reference's per-pair SSE order, everything else the fmaf
-    chain of the GEMM path; the call's n decides, never a page's (include/vlq_ivfpq.h, vlq_flat_*)."""
+    chain of the GEMM path; the call's n decides, never a page's (include/vlq_ivfpq.h, vlq_flat_*).  storage "f16"
+    (GpuIndexFlatConfig::useFloat16): the rows are x.astype(float16), 2 * d bytes each; queries and arithmetic stay float32, so
+    search, refine and compute_distance_subset return bit for bit what an "f32" index over x.astype(float16).astype(float32)
+    returns, and reconstruct_n returns those widened rows.  range_search over "f16" is not built."""
 
     METRICS = GpuIVFPQ.METRICS
+    STORAGES = GpuIVFFlat.STORAGES
     _PREFIX = "vlq_flat_"
 
-    def __init__(self, d, metric="l2", device=0):
+    def __init__(self, d, metric="l2", device=0, storage="f32"):
         self.d, self.device = d, device
         self._h = C.c_void_p()
         if metric not in self.METRICS:
             raise ValueError("metric %r (one of 'l2', 'ip')" % (metric,))
-        self.metric = metric
-        check(lib().vlq_flat_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.METRICS[metric])))
+        if storage not in self.STORAGES:
+            raise ValueError("storage %r (one of 'f32', 'f16')" % (storage,))
+        self.metric, self.storage = metric, storage
+        check(lib().vlq_flat_create_ex(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(self.METRICS[metric]),
+                                       C.c_int(self.STORAGES[storage])))
         self._range_total = 0         # hits the handle holds (range_search)
 
     def reconstruct_n(self, i0=0, n=None, out=None):
@@ -1063,9 +1070,9 @@ class GpuRefineFlat:
     refine store is a GpuFlat of the base's d and metric.  A base label must be a position in the store: add() keeps the two in
     step (IVF bases get the sequential ids ntotal .. ntotal + n - 1); an index whose lists were set with ids 0 .. ntotal - 1
     gets its store from set_store().  The base and the store share one stream of this object's (set_stream replaces it), so the
-    shortlist of a device-side query never leaves the device."""
+    shortlist of a device-side query never leaves the device.  storage "f16": the refine store keeps x.astype(float16)."""
 
-    def __init__(self, base):
+    def __init__(self, base, storage="f32"):
         import torch
         if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat, GpuLSH)):
             raise TypeError("base must be a GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat or GpuLSH, got %s" % type(base).__name__)
@@ -1073,7 +1080,7 @@ class GpuRefineFlat:
         self.d, self.metric, self.device = base.d, base.metric, base.device
         self.k_factor = 1.0
         self.nprobe = 1           # IndexIVF's default, used where search() is given none
-        self.store = GpuFlat(self.d, metric=self.metric, device=self.device)
+        self.store = GpuFlat(self.d, metric=self.metric, device=self.device, storage=storage)
         self._ivf = isinstance(base, (GpuIVFPQ, _GpuIVF))
         self._dev = torch.device("cuda", self.device)
         self._stream = torch.cuda.Stream(device=self._dev)
