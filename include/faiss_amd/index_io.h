@@ -8,6 +8,8 @@
 //   "IxSQ"  IndexScalarQuantizer (index_io.cpp:271-275, :604-610): header, the ScalarQuantizer, the codes
 //   "IxPq"  IndexPQ (index_io.cpp:259-270); read as well: its older records "IxPQ" and "IxPo" (:578-596)
 //   "IxRF"  IndexRefineFlat (index_io.cpp:336-341, :645-654): header, the base index, the refine IndexFlat, k_factor
+//   "IxPT"  IndexPreTransform (index_io.cpp:318-327, :625-639): header, the number of transforms, one transform record each
+//           ("rrot" / "PcAm" / "PCAm" / "LTra" / "RmDT" / "VNrm", index_io.cpp:158-199, :386-429), the sub-index
 //   "IxHe"  IndexLSH (index_io.cpp:248-258); read as well: its older record "IxHE" (:549-575).  Its rotation is the one
 //           VectorTransform record built here, "rrot" (index_io.cpp:159-175, :189-193, :391-410, :425-427)
 // Files written by the reference load here and vice versa (tests/test_index_io.py checks
@@ -109,10 +111,84 @@ inline void read_rrot(RandomRotationMatrix& lt, FILE* f) {
   r1(f, lt.d_in); r1(f, lt.d_out); r1(f, lt.is_trained);
 }
 
+// every transform record (index_io.cpp:158-199, :386-429): "rrot", "PcAm" (read as well: its older form "PCAm", without
+// balanced_bins), "LTra" (any other LinearTransform, OPQ included), "RmDT", "VNrm"; then d_in, d_out, is_trained
+inline void write_VectorTransform(const VectorTransform* vt, FILE* f) {
+  if (const LinearTransform* lt = dynamic_cast<const LinearTransform*>(vt)) {
+    if (dynamic_cast<const RandomRotationMatrix*>(lt)) {
+      w1(f, fourcc("rrot"));
+    } else if (const PCAMatrix* pca = dynamic_cast<const PCAMatrix*>(lt)) {
+      w1(f, fourcc("PcAm"));
+      w1(f, pca->eigen_power); w1(f, pca->random_rotation); w1(f, pca->balanced_bins);
+      wvec(f, pca->mean); wvec(f, pca->eigenvalues); wvec(f, pca->PCAMat);
+    } else {
+      w1(f, fourcc("LTra"));
+    }
+    w1(f, lt->have_bias);
+    wvec(f, lt->A);
+    wvec(f, lt->b);
+  } else if (const RemapDimensionsTransform* rdt = dynamic_cast<const RemapDimensionsTransform*>(vt)) {
+    w1(f, fourcc("RmDT"));
+    wvec(f, rdt->map);
+  } else if (const NormalizationTransform* nt = dynamic_cast<const NormalizationTransform*>(vt)) {
+    w1(f, fourcc("VNrm"));
+    w1(f, nt->norm);
+  } else {
+    FAISS_THROW_MSG("cannot serialize this");
+  }
+  w1(f, vt->d_in); w1(f, vt->d_out); w1(f, vt->is_trained);
+}
+inline VectorTransform* read_VectorTransform(FILE* f) {
+  uint32_t h;
+  r1(f, h);
+  std::unique_ptr<VectorTransform> vt;
+  if (h == fourcc("rrot") || h == fourcc("PCAm") || h == fourcc("PcAm") || h == fourcc("LTra")) {
+    LinearTransform* lt;
+    if (h == fourcc("rrot")) {
+      lt = new RandomRotationMatrix();
+      vt.reset(lt);
+    } else if (h == fourcc("LTra")) {
+      lt = new LinearTransform();
+      vt.reset(lt);
+    } else {
+      PCAMatrix* pca = new PCAMatrix();
+      vt.reset(pca);
+      r1(f, pca->eigen_power); r1(f, pca->random_rotation);
+      if (h == fourcc("PcAm")) r1(f, pca->balanced_bins);
+      rvec(f, pca->mean); rvec(f, pca->eigenvalues); rvec(f, pca->PCAMat);
+      lt = pca;
+    }
+    r1(f, lt->have_bias);
+    rvec(f, lt->A);
+    rvec(f, lt->b);
+  } else if (h == fourcc("RmDT")) {
+    RemapDimensionsTransform* rdt = new RemapDimensionsTransform();
+    vt.reset(rdt);
+    rvec(f, rdt->map);
+  } else if (h == fourcc("VNrm")) {
+    NormalizationTransform* nt = new NormalizationTransform();
+    vt.reset(nt);
+    r1(f, nt->norm);
+  } else {
+    FAISS_THROW_MSG("fourcc not recognized");
+  }
+  r1(f, vt->d_in); r1(f, vt->d_out); r1(f, vt->is_trained);
+  return vt.release();
+}
+
 }  // namespace io_detail
 
 inline void write_index(const Index* idx, FILE* f) {
   using namespace io_detail;
+  if (const IndexPreTransform* ixpt = dynamic_cast<const IndexPreTransform*>(idx)) {
+    w1(f, fourcc("IxPT"));                     // index_io.cpp:318-327
+    write_header(idx, f);
+    const int nt = (int)ixpt->chain.size();
+    w1(f, nt);
+    for (const VectorTransform* t : ixpt->chain) write_VectorTransform(t, f);
+    write_index(ixpt->index, f);
+    return;
+  }
   if (const IndexFlat* flat = dynamic_cast<const IndexFlat*>(idx)) {
     w1(f, fourcc(flat->metric_type == METRIC_L2 ? "IxF2" : "IxFI"));     // index_io.cpp:166-171
     write_header(idx, f);
@@ -215,6 +291,17 @@ inline Index* read_index(FILE* f, bool precompute = true) {
     rvec(f, flat->xb);
     FAISS_THROW_IF_NOT(flat->xb.size() == (size_t)flat->ntotal * flat->d);
     return flat.release();
+  }
+  if (h == fourcc("IxPT")) {                   // index_io.cpp:625-639 (the current format: the number of transforms is stored)
+    std::unique_ptr<IndexPreTransform> ixpt(new IndexPreTransform());
+    ixpt->own_fields = true;
+    read_header(ixpt.get(), f);
+    int nt;
+    r1(f, nt);
+    FAISS_THROW_IF_NOT(nt >= 0 && nt < 1024);
+    for (int i = 0; i < nt; i++) ixpt->chain.push_back(read_VectorTransform(f));
+    ixpt->index = read_index(f, precompute);
+    return ixpt.release();
   }
   if (h == fourcc("IxRF")) {                   // index_io.cpp:645-654
     std::unique_ptr<IndexRefineFlat> idxrf(new IndexRefineFlat());

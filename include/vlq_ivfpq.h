@@ -816,6 +816,53 @@ int vlq_lsh_set_scan_split(vlq_lsh_t h, int query_tile, int slices);
  *   "kernel=scan_hamming_kernel<2, 1, 16> Q=2 S=4 slice=250000 page=32768 lds=4368 join=1".  Synchronises the stream. */
 int vlq_lsh_last_scan_info(vlq_lsh_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Vector transforms: what faiss::IndexPreTransform (VectorTransform.h:250-300, VectorTransform.cpp:786-1002) runs in front of
+ * an index on every add, search and reconstruct, on the device.  One handle is one transform of d_in -> d_out floats:
+ *   VLQ_TRANSFORM_LINEAR  LinearTransform (and what PCAMatrix / OPQMatrix / RandomRotationMatrix prepare into A and b).
+ *     apply (apply_noalloc, VectorTransform.cpp:105-131): xt[r][j] = the fmaf chain over i = 0 .. d_in-1 ascending of
+ *       A[j][i] * x[r][i], STARTING from b[j] (from 0.0f without a bias), A [d_out][d_in] row-major.  The reference hands this
+ *       to sgemm_, whose order is the BLAS vendor's; the chain is this library's standing definition (vlq_lsh_apply, the
+ *       shell's host LinearTransform::apply_noalloc), and every kernel behind this call gives its bits, whatever n.
+ *     reverse (transform_transpose, :134-158, through reverse_transform, :199-207): x[r][i] = the fmaf chain over
+ *       j = 0 .. d_out-1 ascending from 0.0f of A[j][i] * (y[r][j] - b[j]), the subtraction rounded first.  Only for a matrix
+ *       set with is_orthonormal (the host's finding: set_is_orthonormal, :160-196); VLQ_ERR_INVALID otherwise (:205 throws).
+ *   VLQ_TRANSFORM_REMAP   RemapDimensionsTransform: apply (:1043-1053) xt[j] = map[j] < 0 ? 0 : x[map[j]]; reverse (:1055-1066)
+ *     zero-fills x, then x[map[j]] = xt[j] for j ascending (the last j wins where a source is mapped twice).
+ *   VLQ_TRANSFORM_L2NORM  NormalizationTransform with norm 2 (:765-780, fvec_renorm_L2, utils.cpp:686-701), d_in == d_out:
+ *     nr = fvec_norm_L2sqr in the SSE order; if nr > 0 every component is multiplied by (float)(1.0 / sqrtf(nr)).  The reverse
+ *     is a copy (:776-780).
+ * Served: 1 <= d_in, d_out <= VLQ_TRANSFORM_MAX_D (VLQ_ERR_UNSUPPORTED beyond), any n >= 0.  Device rows on both sides take one
+ * launch over all of them (no workspace); rows that come from or go to host memory are staged in pages of 32 768.
+ * apply / reverse before the matrix or the map is set: VLQ_ERR_STATE.  x and xt [h|d] and must not overlap; device outputs are
+ * written on the handle's stream without synchronising, host outputs are there on return. */
+typedef struct vlq_transform_s* vlq_transform_t;
+enum { VLQ_TRANSFORM_LINEAR = 0, VLQ_TRANSFORM_REMAP = 1, VLQ_TRANSFORM_L2NORM = 2 };
+#define VLQ_TRANSFORM_MAX_D 4096
+
+/* VectorTransform::VectorTransform (VectorTransform.h:36-38); L2NORM with d_in != d_out: VLQ_ERR_INVALID */
+int vlq_transform_create(vlq_transform_t* out, int device, int kind, int d_in, int d_out);
+void vlq_transform_destroy(vlq_transform_t h);
+/* the stream apply and reverse issue their work on (synchronises the old one first).  Not named set_stream: the handles with
+ * a vlq_<kind>_set_stream are the index handles, held to the stream-ordered search contract of tests/async_cases.py; a transform
+ * has no search, its stream-ordered use is tested beside its kernels */
+int vlq_transform_use_stream(vlq_transform_t h, void* hip_stream);
+/* LinearTransform::A [d_out*d_in], b [d_out] or NULL = have_bias false, is_orthonormal (VectorTransform.h:73-83) [h|d].  The
+ * transposed copy the reverse reads is made here, on the device. */
+int vlq_transform_set_linear(vlq_transform_t h, const float* A, const float* b, int is_orthonormal);
+/* RemapDimensionsTransform::map [d_out] (VectorTransform.h:222), host; an entry < -1 or >= d_in: VLQ_ERR_INVALID (:1017) */
+int vlq_transform_set_map(vlq_transform_t h, const int* map);
+/* VectorTransform::apply_noalloc: x[n*d_in] -> xt[n*d_out] */
+int vlq_transform_apply(vlq_transform_t h, int64_t n, const float* x, float* xt);
+/* VectorTransform::reverse_transform: xt[n*d_out] -> x[n*d_in] */
+int vlq_transform_reverse(vlq_transform_t h, int64_t n, const float* xt, float* x);
+/* Introspection, speed only: the last launch of apply / reverse as text,
+ *   "kernel=linear_strip_kernel<true> rows=128 panel=128 kc=32 resident=1 lds=110592 small_n=16 max_resident_d=224".
+ * rows: the strip of rows one workgroup owns; panel: columns at a time; kc: floats of d_in per step; resident: the strip stays
+ * in LDS across the panels (d_in <= max_resident_d); small_n: the batch size up to which linear_rows_kernel runs instead.
+ * Before any launch the text is the plan of 32 768 rows.  Synchronises the stream. */
+int vlq_transform_last_info(vlq_transform_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

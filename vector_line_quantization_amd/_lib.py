@@ -51,6 +51,9 @@ SYMBOLS = [
     "vlq_lsh_create", "vlq_lsh_destroy", "vlq_lsh_set_stream", "vlq_lsh_set_rotation", "vlq_lsh_set_thresholds", "vlq_lsh_apply",
     "vlq_lsh_encode", "vlq_lsh_add", "vlq_lsh_add_codes", "vlq_lsh_get_codes", "vlq_lsh_ntotal", "vlq_lsh_reset",
     "vlq_lsh_reserve_memory", "vlq_lsh_search", "vlq_lsh_search_codes", "vlq_lsh_set_scan_split", "vlq_lsh_last_scan_info",
+    # vector transforms in front of an index (vlq_transform_t)
+    "vlq_transform_create", "vlq_transform_destroy", "vlq_transform_use_stream", "vlq_transform_set_linear", "vlq_transform_set_map",
+    "vlq_transform_apply", "vlq_transform_reverse", "vlq_transform_last_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -126,6 +129,7 @@ def lib():
         L.vlq_flat_destroy.restype = None
         L.vlq_lsh_ntotal.restype = C.c_int64
         L.vlq_lsh_destroy.restype = None
+        L.vlq_transform_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -1187,6 +1187,193 @@ class GpuRefineFlat:
         return self.store.last_refine_info()
 
 
+class _GpuTransform:
+    """What the three vector transforms share (include/vlq_ivfpq.h, vlq_transform_*): a handle of d_in -> d_out floats with
+    apply and reverse.  Rows may be numpy arrays or torch tensors; a device output is written on the transform's stream without
+    synchronising, a host output is complete on return."""
+
+    _PREFIX = "vlq_transform_"
+    _KINDS = {"linear": 0, "remap": 1, "l2norm": 2}
+    _call = _GpuOneList._call
+    close = _GpuOneList.close
+    __del__ = _GpuOneList.__del__
+    _out = GpuIVFPQ._out
+
+    def __init__(self, kind, d_in, d_out, device):
+        self.d_in, self.d_out, self.device = d_in, d_out, device
+        self._h = C.c_void_p()
+        check(lib().vlq_transform_create(C.byref(self._h), C.c_int(device), C.c_int(self._KINDS[kind]), C.c_int(d_in), C.c_int(d_out)))
+
+    def set_stream(self, stream_ptr):
+        self._call("use_stream", C.c_void_p(stream_ptr or 0))
+
+    def _run(self, name, x, width_in, width_out, out):
+        if x.ndim != 2 or x.shape[1] != width_in:
+            raise ValueError("rows of %d floats expected, got shape %s" % (width_in, tuple(x.shape)))
+        n = x.shape[0]
+        px, _a = _ptr(x, np.float32)
+        out = self._out(out, (n, width_out), np.float32, x)
+        self._call(name, C.c_int64(n), px, _out_ptr(out, np.float32)[0])
+        return out
+
+    def apply(self, x, out=None):
+        """VectorTransform::apply: [n][d_in] -> [n][d_out]"""
+        return self._run("apply", x, self.d_in, self.d_out, out)
+
+    def reverse(self, xt, out=None):
+        """VectorTransform::reverse_transform: [n][d_out] -> [n][d_in]"""
+        return self._run("reverse", xt, self.d_out, self.d_in, out)
+
+    def last_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
+class GpuLinearTransform(_GpuTransform):
+    """faiss::LinearTransform (and the A, b that PCAMatrix, OPQMatrix and RandomRotationMatrix prepare): xt = b + A x with A
+    [d_out][d_in], every output the fmaf chain over i ascending starting from b[j].  reverse is transform_transpose and needs
+    is_orthonormal (the caller's finding, LinearTransform::set_is_orthonormal); without it reverse raises."""
+
+    def __init__(self, d_in, d_out, A, b=None, is_orthonormal=False, device=0):
+        super().__init__("linear", d_in, d_out, device)
+        if tuple(A.shape) != (d_out, d_in) or (b is not None and tuple(b.shape) != (d_out,)):
+            raise ValueError("A must be [d_out=%d][d_in=%d] and b [d_out]" % (d_out, d_in))
+        self.is_orthonormal = bool(is_orthonormal)
+        pa, _a = _ptr(A, np.float32)
+        pb, _b = _ptr(b, np.float32)
+        self._call("set_linear", pa, pb, C.c_int(int(self.is_orthonormal)))
+
+
+class GpuRemapDimensions(_GpuTransform):
+    """faiss::RemapDimensionsTransform: xt[j] = x[map[j]], 0 where map[j] is -1; reverse zero-fills and scatters back"""
+
+    def __init__(self, d_in, d_out, map, device=0):
+        super().__init__("remap", d_in, d_out, device)
+        m = np.ascontiguousarray(map, dtype=np.int32)
+        if m.shape != (d_out,):
+            raise ValueError("map must have d_out=%d entries" % d_out)
+        self._call("set_map", m.ctypes.data_as(C.c_void_p))
+
+
+class GpuNormalization(_GpuTransform):
+    """faiss::NormalizationTransform with norm 2 ("L2norm" of index_factory): rows scaled to unit length, zero rows kept; reverse
+    is a copy"""
+
+    def __init__(self, d, device=0):
+        super().__init__("l2norm", d, d, device)
+
+
+class GpuPreTransform:
+    """faiss::IndexPreTransform (VectorTransform.h:250-300): a chain of transforms, applied first to last, in front of a base
+    index -- any class GpuRefineFlat accepts, or a GpuRefineFlat.  add and search transform their rows on the device and hand
+    the base a device tensor; reconstruct_n runs the chain's reverses last to first.  The chain and the base share one stream of
+    this object's (set_stream replaces it) and the intermediate rows are device tensors reused while the shape holds, so a
+    device-resident batch never leaves the device between the transform and the scan.  An empty chain is the base itself.
+    Not built: train, search_and_reconstruct, remove_ids."""
+
+    def __new__(cls, chain, base):
+        return base if len(chain) == 0 else super().__new__(cls)
+
+    def __init__(self, chain, base):
+        import torch
+        if not isinstance(base, (GpuIVFPQ, GpuIVFFlat, GpuIVFSQ, GpuPQ, GpuSQ, GpuFlat, GpuLSH, GpuRefineFlat)):
+            raise TypeError("base must be one of the Gpu index classes or a GpuRefineFlat, got %s" % type(base).__name__)
+        self.chain, self.base = list(chain), base
+        for t, d_next in zip(self.chain, [t.d_in for t in self.chain[1:]] + [base.d]):
+            if t.d_out != d_next:
+                raise ValueError("the chain does not meet: a transform of d_out=%d in front of d=%d" % (t.d_out, d_next))
+        self.d, self.device = self.chain[0].d_in, base.device
+        self._ivf = isinstance(base, (GpuIVFPQ, _GpuIVF))
+        self._refine = isinstance(base, GpuRefineFlat)
+        self.nprobe = 1           # IndexIVF's default, used where search() over an IVF base is given none (a GpuRefineFlat has its own)
+        self._dev = torch.device("cuda", self.device)
+        self._stream = torch.cuda.Stream(device=self._dev)
+        self.set_stream(self._stream.cuda_stream)
+        self._rows = {}           # intermediate rows by (direction, stage)
+
+    def set_stream(self, stream_ptr):
+        for t in self.chain:
+            t.set_stream(stream_ptr)
+        self.base.set_stream(stream_ptr)
+        self._stream_ptr = stream_ptr
+
+    @property
+    def ntotal(self):
+        return self.base.ntotal
+
+    def _buf(self, key, n, d):
+        import torch
+        b = self._rows.get(key)
+        if b is None or b.shape != (n, d):
+            # torch's allocator knows these rows by the stream they were allocated on, the library uses them on this object's:
+            # the rows they replace may still be read there, so that stream is waited for before they go back to the allocator
+            if b is not None:
+                self._stream_sync()
+            b = self._rows[key] = torch.empty((n, d), dtype=torch.float32, device=self._dev)
+        return b
+
+    def _stream_sync(self):
+        import torch
+        if self._stream_ptr:
+            torch.cuda.ExternalStream(self._stream_ptr, device=self._dev).synchronize()
+        else:
+            torch.cuda.synchronize(self._dev)
+
+    def apply_chain(self, x):
+        """IndexPreTransform::apply_chain: the rows the base sees, a device tensor of this object's"""
+        for i, t in enumerate(self.chain):
+            x = t.apply(x, self._buf(("apply", i), x.shape[0], t.d_out))
+        return x
+
+    def reverse_chain(self, xt, out=None):
+        """IndexPreTransform::reverse_chain: last transform first; the final rows go to `out` (default: a numpy array)"""
+        for i in range(len(self.chain) - 1, 0, -1):
+            xt = self.chain[i].reverse(xt, self._buf(("reverse", i), xt.shape[0], self.chain[i].d_in))
+        return self.chain[0].reverse(xt, np.empty((xt.shape[0], self.d), np.float32) if out is None else out)
+
+    def add(self, x, xids=None):
+        xt = self.apply_chain(x)
+        if self._ivf or self._refine:
+            self.base.add(xt, xids)
+        elif xids is not None:
+            raise ValueError("%s labels its vectors by position: no ids" % type(self.base).__name__)
+        else:
+            self.base.add(xt)
+
+    def search(self, x, k, nprobe=None, D=None, I=None):
+        n = x.shape[0]
+        xt = self.apply_chain(x)
+        host = not (_is_torch(x) and x.is_cuda)
+        if self._refine:
+            if not host:
+                return self.base.search(xt, k, nprobe, D, I)
+            Dd, Id = self.base.search(xt, k, nprobe)      # (the refine synchronises the stream: the rows are complete)
+            D = np.empty((n, k), np.float32) if D is None else D
+            I = np.empty((n, k), np.int64) if I is None else I
+            D[...], I[...] = Dd.cpu().numpy(), Id.cpu().numpy()
+            return D, I
+        if host:                                   # host queries: host rows, complete on return
+            D = np.empty((n, k), np.float32) if D is None else D
+            I = np.empty((n, k), np.int64) if I is None else I
+        if self._ivf:
+            return self.base.search(xt, self.nprobe if nprobe is None else nprobe, k, D, I)
+        return self.base.search(xt, k, D, I)
+
+    def reconstruct_n(self, i0=0, n=None):
+        """IndexPreTransform::reconstruct_n: the base's rows through reverse_chain, [n][d] float32 on the host"""
+        if not hasattr(self.base, "reconstruct_n"):
+            raise ValueError("%s has no reconstruct_n" % type(self.base).__name__)
+        n = self.ntotal - i0 if n is None else n
+        return self.reverse_chain(self.base.reconstruct_n(i0, n, self._buf(("reconstruct", 0), n, self.base.d)))
+
+    def reset(self):
+        if hasattr(self.base, "reset"):
+            self.base.reset()
+        else:       # GpuIVFPQ: empty lists
+            self.base.set_lists(np.zeros((0, self.base.M), np.uint8), np.zeros((0,), np.int64), np.zeros((self.base.nlist + 1,), np.int64))
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
