@@ -863,6 +863,58 @@ int vlq_transform_reverse(vlq_transform_t h, int64_t n, const float* xt, float* 
  * Before any launch the text is the plan of 32 768 rows.  Synchronises the stream. */
 int vlq_transform_last_info(vlq_transform_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * k-means: faiss::Clustering::train (Clustering.cpp:66-206) with km_update_centroids (utils.cpp:1369-1450), on the device
+ * (csrc/kmeans.hip, csrc/kmeans_plan.h).  One handle is one problem shape: k centroids of d floats.
+ *   update (the step after an assignment): centroid c, component j = ONE fp32 chain from 0.0f over the rows with assign[i] == c,
+ *     i ascending, divided by (float)count[c]; an empty cluster is zeros.  Bit for bit the reference's, whatever its thread count.
+ *   empty clusters, ci ascending: a generator seeded 1234 on every call; cj = 0, 1, .. (mod k) until
+ *     rand_float() < (float)((count[cj] - 1.0) / (float)(n - k)); row cj is copied to row ci, ci multiplied by 1 + 1/1024. on
+ *     even components and 1 - 1/1024. on odd ones, cj the other way round (the product in double, rounded to float);
+ *     count[ci] = count[cj] / 2, count[cj] -= count[ci].  The generator is glibc's random_r over an 8-byte state:
+ *     s = (s * 1103515245 + 12345) & 0x7fffffff from the seed, rand_float() = s / 2^31.  Decided on the host from the counts,
+ *     which are read only when the device flag says a cluster is empty; the rows change on the device.
+ *   train: more than k * max_points_per_centroid rows are subsampled to x[perm[0 ..]], perm = rand_perm(n, seed)
+ *     (utils.cpp:307-317); the initial centroids are x[perm[0 .. k)] with rand_perm(n, seed + 1 + redo * 15486557) unless
+ *     vlq_kmeans_set_centroids provided them; spherical: fvec_renorm_L2 of the centroids after the initialisation and after every
+ *     update; niter times: assignment, objective, update; nredo > 1 keeps the run whose LAST objective is smallest.
+ *   The assignment of every iteration is exactly vlq_flat_create(d, L2) + vlq_flat_add(centroids) + vlq_flat_search(n, x, 1)
+ *   over the (subsampled) rows -- not the reference's BLAS.  The objective is the sum of that search's distances in double, in
+ *   an order that depends on n only -- not the reference's sequential float sum.  So every step is defined bit for bit, and a
+ *   whole run repeats bit for bit, but a run is not claimed to equal the reference's for a seed.
+ * Rows, labels and centroids stay on the device through the loop.  Limits: n < 2^31, k * d < 2^31.  Pointers [h|d]. */
+typedef struct vlq_kmeans_s* vlq_kmeans_t;
+
+int vlq_kmeans_create(vlq_kmeans_t* out, int device, int d, int64_t k);
+void vlq_kmeans_destroy(vlq_kmeans_t h);
+/* the stream every call issues its work on (synchronises the old one first).  Not named set_stream, as vlq_transform_use_stream
+ * is not: a k-means handle is no index and has no stream-ordered search contract */
+int vlq_kmeans_use_stream(vlq_kmeans_t h, void* hip_stream);
+/* ClusteringParameters (Clustering.h): the defaults are niter 25, nredo 1, spherical 0, max_points_per_centroid 256, seed 1234 */
+int vlq_kmeans_set_params(vlq_kmeans_t h, int niter, int nredo, int spherical, int64_t max_points_per_centroid, int64_t seed);
+/* Clustering::centroids provided before train: centroids[k*d] [h|d] is the initialisation (and what assign searches until a
+ * train); NULL: back to the random initialisation.  Synchronises the stream. */
+int vlq_kmeans_set_centroids(vlq_kmeans_t h, const float* centroids);
+/* Clustering::train on x[n*d] [h|d].  VLQ_ERR_INVALID: n < k, a NaN or infinity in x (found on the device), nredo > 1 with
+ * provided centroids.  Synchronises the stream. */
+int vlq_kmeans_train(vlq_kmeans_t h, int64_t n, const float* x);
+/* out[k*d] [h|d].  Synchronises the stream. */
+int vlq_kmeans_get_centroids(vlq_kmeans_t h, float* out);
+/* Clustering::obj of the last train: *count = niter * nredo entries, the first min(cap, *count) of them into out (host) */
+int vlq_kmeans_objective(vlq_kmeans_t h, double* out, int cap, int* count);
+/* the nearest centroid of x[n*d]: D[n], I[n] [h|d], vlq_flat_search with k = 1 over the centroids */
+int vlq_kmeans_assign(vlq_kmeans_t h, int64_t n, const float* x, float* D, int64_t* I);
+/* km_update_centroids on its own: x[n*d], assign[n] -> centroids_inout[k*d] (overwritten: the reference zeroes them first),
+ * counts_out[k] after the splits (or NULL), *nsplit_out; all but nsplit_out [h|d].  A label outside 0 .. k-1: VLQ_ERR_INVALID,
+ * found by a device flag; no label is ever used as an index.  n < k: VLQ_ERR_INVALID.  Synchronises the stream. */
+int vlq_kmeans_update(vlq_kmeans_t h, int64_t n, const float* x, const int64_t* assign, float* centroids_inout, int64_t* counts_out,
+                      int* nsplit_out);
+/* Introspection, speed only: the last update step as text,
+ *   "kernel=kmeans_update_kernel waves=2 slices=2 id_batch=256 unroll=8 group=radix_sort key_bits=32 n=1048576 nsplit=0
+ *    group_ms=0.2 update_ms=0.3"
+ * (group_ms, update_ms: the stream time of the step's grouping and of its update kernel, from events).  Synchronises the stream. */
+int vlq_kmeans_last_info(vlq_kmeans_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,9 @@ SYMBOLS = [
     # vector transforms in front of an index (vlq_transform_t)
     "vlq_transform_create", "vlq_transform_destroy", "vlq_transform_use_stream", "vlq_transform_set_linear", "vlq_transform_set_map",
     "vlq_transform_apply", "vlq_transform_reverse", "vlq_transform_last_info",
+    # k-means (vlq_kmeans_t)
+    "vlq_kmeans_create", "vlq_kmeans_destroy", "vlq_kmeans_use_stream", "vlq_kmeans_set_params", "vlq_kmeans_set_centroids", "vlq_kmeans_train",
+    "vlq_kmeans_get_centroids", "vlq_kmeans_objective", "vlq_kmeans_assign", "vlq_kmeans_update", "vlq_kmeans_last_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -130,6 +133,7 @@ def lib():
         L.vlq_lsh_ntotal.restype = C.c_int64
         L.vlq_lsh_destroy.restype = None
         L.vlq_transform_destroy.restype = None
+        L.vlq_kmeans_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

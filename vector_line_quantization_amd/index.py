@@ -1374,6 +1374,94 @@ class GpuPreTransform:
             self.base.set_lists(np.zeros((0, self.base.M), np.uint8), np.zeros((0,), np.int64), np.zeros((self.base.nlist + 1,), np.int64))
 
 
+class GpuKMeans:
+    """faiss::Clustering (Clustering.h, Clustering.cpp:66-206) on the device: k centroids of d floats by Lloyd's iterations
+    (include/vlq_ivfpq.h, vlq_kmeans_*).  The assignment is GpuFlat(d).search(x, 1) over the centroids; the update is
+    km_update_centroids bit for bit -- per (centroid, component) one float32 chain over the centroid's rows in ascending order,
+    then the reference's empty-cluster splits.  Rows may be numpy arrays or torch tensors; outputs follow the input's device."""
+
+    _PREFIX = "vlq_kmeans_"
+    _call = _GpuOneList._call
+    close = _GpuOneList.close
+    __del__ = _GpuOneList.__del__
+    _out = GpuIVFPQ._out
+
+    def __init__(self, d, k, niter=25, nredo=1, spherical=False, max_points_per_centroid=256, seed=1234, device=0):
+        self.d, self.k, self.device = d, k, device
+        self._h = C.c_void_p()
+        check(lib().vlq_kmeans_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int64(k)))
+        self._call("set_params", C.c_int(niter), C.c_int(nredo), C.c_int(int(spherical)), C.c_int64(max_points_per_centroid), C.c_int64(seed))
+
+    def set_stream(self, stream_ptr):
+        self._call("use_stream", C.c_void_p(stream_ptr or 0))
+
+    def _rows(self, x):
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError("rows of %d floats expected, got shape %s" % (self.d, tuple(x.shape)))
+        return x.shape[0], _ptr(x, np.float32)
+
+    def train(self, x, init=None):
+        """Clustering::train: the centroids [k][d] (on x's device).  init [k][d]: the initial centroids instead of random rows"""
+        n, (px, _a) = self._rows(x)
+        if init is not None and tuple(init.shape) != (self.k, self.d):
+            raise ValueError("init must be [k=%d][d=%d]" % (self.k, self.d))
+        pi, _b = _ptr(init, np.float32)
+        self._call("set_centroids", pi)
+        self._call("train", C.c_int64(n), px)
+        self._like = x
+        return self.centroids
+
+    @property
+    def centroids(self):
+        out = self._out(None, (self.k, self.d), np.float32, getattr(self, "_like", None))
+        self._call("get_centroids", _out_ptr(out, np.float32)[0])
+        return out
+
+    @property
+    def obj(self):
+        """Clustering::obj: the objective in front of every update of the last train, over all runs of nredo"""
+        cnt = C.c_int(0)
+        self._call("objective", None, C.c_int(0), C.byref(cnt))
+        out = np.empty((cnt.value,), np.float64)
+        self._call("objective", out.ctypes.data_as(C.c_void_p), C.c_int(cnt.value), C.byref(cnt))
+        return out
+
+    def assign(self, x):
+        """(D [n], I [n]): squared distance to and label of the nearest centroid"""
+        n, (px, _a) = self._rows(x)
+        D = self._out(None, (n,), np.float32, x)
+        I = self._out(None, (n,), np.int64, x)
+        self._call("assign", C.c_int64(n), px, _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def update(self, x, assign, centroids=None):
+        """km_update_centroids: (centroids [k][d], counts [k] after the splits, nsplit).  `centroids` is overwritten in place when
+        given (the reference zeroes it first); a label outside 0 .. k-1 raises."""
+        n, (px, _a) = self._rows(x)
+        if tuple(assign.shape) != (n,):
+            raise ValueError("assign must be [n=%d]" % n)
+        pa, _b = _ptr(assign, np.int64)
+        centroids = self._out(centroids, (self.k, self.d), np.float32, x)
+        counts = self._out(None, (self.k,), np.int64, x)
+        nsplit = C.c_int(0)
+        self._call("update", C.c_int64(n), px, pa, _out_ptr(centroids, np.float32)[0], _out_ptr(counts, np.int64)[0], C.byref(nsplit))
+        return centroids, counts, nsplit.value
+
+    def last_info(self):
+        buf = C.create_string_buffer(256)
+        self._call("last_info", buf, C.c_int(256))
+        return buf.value.decode()
+
+
+def kmeans(x, k, **kw):
+    """The centroids [k][d] of GpuKMeans(d, k, **kw).train(x)"""
+    km = GpuKMeans(x.shape[1], k, **kw)
+    try:
+        return km.train(x)
+    finally:
+        km.close()
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
