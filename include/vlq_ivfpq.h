@@ -915,6 +915,59 @@ int vlq_kmeans_update(vlq_kmeans_t h, int64_t n, const float* x, const int64_t* 
  * (group_ms, update_ms: the stream time of the step's grouping and of its update kernel, from events).  Synchronises the stream. */
 int vlq_kmeans_last_info(vlq_kmeans_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Product-quantizer training: faiss::ProductQuantizer::train (ProductQuantizer.cpp:236-308) on the device (csrc/pq_train.hip,
+ * csrc/pq_train_plan.h).  One handle is one shape: M sub-quantizers of 2^nbits centroids of d / M floats.
+ *   Definition: for every m, the codebook cb[m] and the objective sequence equal, bit for bit, those of a vlq_kmeans handle
+ *     (d / M, 2^nbits, the same parameters) trained on the contiguous copy of the columns m d/M .. (m + 1) d/M - 1 of x -- the
+ *     subsample, spherical, nredo (every slice keeps ITS best run) and the empty-cluster splits included.
+ *   Routes (vlq_pqtrain_last_info names the one taken):
+ *     batched  one pq_assign_kernel launch per iteration scores every row's M slices against the M codebooks, in place (x is
+ *              read once, no slice copy exists); one grouping and one ordered update run over the view [n M][d / M] with labels
+ *              m 2^nbits + c; the splits are planned per slice on the host; one status read per iteration.
+ *     loop     M vlq_kmeans runs over slice copies.  Taken when the training set, after the subsample, has fewer than 20 rows and
+ *              d / M is a multiple of 4 (the flat search takes its per-pair order there), and when one slice's codebook does not
+ *              fit LDS beside the row tile (d / M beyond about 96 at 8 bits).
+ *   Train types (ProductQuantizer::train_type_t): default; hot start (the handle's current codebook is the initialisation);
+ *     shared (one k-means over the view [n M][d / M], its centroids in every slice).  The two hypercube initialisations are not
+ *     built: VLQ_ERR_UNSUPPORTED.
+ * IndexIVFPQ::train is composed of vlq_kmeans_*, vlq_flat_search and the calls below by the Python handle (GpuIVFPQ.train), for a
+ * flat coarse quantizer.  Not built: a multi-index (IMI) coarse quantizer, IVFPQR's second-level residuals, polysemous training.
+ * Limits: nbits <= 8, n < 2^31, n M < 2^31 (after the subsample).  Pointers [h|d]. */
+typedef struct vlq_pqtrain_s* vlq_pqtrain_t;
+enum { VLQ_PQ_TRAIN_DEFAULT = 0, VLQ_PQ_TRAIN_HOT_START = 1, VLQ_PQ_TRAIN_SHARED = 2, VLQ_PQ_TRAIN_HYPERCUBE = 3, VLQ_PQ_TRAIN_HYPERCUBE_PCA = 4 };
+
+int vlq_pqtrain_create(vlq_pqtrain_t* out, int device, int d, int M, int nbits);
+void vlq_pqtrain_destroy(vlq_pqtrain_t h);
+/* the stream every call issues its work on (synchronises the old one first); not named set_stream, as vlq_kmeans_use_stream is not */
+int vlq_pqtrain_use_stream(vlq_pqtrain_t h, void* hip_stream);
+/* ClusteringParameters of every sub-quantizer's k-means: vlq_kmeans_set_params */
+int vlq_pqtrain_set_params(vlq_pqtrain_t h, int niter, int nredo, int spherical, int64_t max_points_per_centroid, int64_t seed);
+int vlq_pqtrain_set_train_type(vlq_pqtrain_t h, int train_type);
+/* ProductQuantizer::centroids [M][ksub][dsub], the layout of vlq_ivfpq_set_pq_centroids.  Synchronises the stream. */
+int vlq_pqtrain_set_centroids(vlq_pqtrain_t h, const float* centroids);
+int vlq_pqtrain_get_centroids(vlq_pqtrain_t h, float* out);
+/* ProductQuantizer::train on x[n*d].  VLQ_ERR_INVALID: n < 2^nbits, a NaN or infinity in x (found on the device), nredo > 1 with
+ * a hot start.  VLQ_ERR_STATE: a hot start without a codebook.  Synchronises the stream. */
+int vlq_pqtrain_train(vlq_pqtrain_t h, int64_t n, const float* x);
+/* the objectives of the last train, [M][niter * nredo] (host): *count entries in all, the first min(cap, *count) into out */
+int vlq_pqtrain_objective(vlq_pqtrain_t h, double* out, int cap, int* count);
+/* the assignment on its own against the current codebook: I[n*M], I[i*M + m] = m 2^nbits + the nearest centroid of slice m of
+ * row i (the update's labels), D[M*n] slice-major, D[m*n + i] its squared distance: vlq_flat_search at k = 1 per slice, bit for
+ * bit, under the same two routes */
+int vlq_pqtrain_assign(vlq_pqtrain_t h, int64_t n, const float* x, float* D, int64_t* I);
+/* the parts of IndexIVFPQ::train_residual_o (IndexIVFPQ.cpp:73-131) around the PQ training, over rows of d floats:
+ * out[m*d] = x[perm[0 .. m)], perm = rand_perm(n, seed); out[n*d] = x[i] - centroids[assign[i]], one float subtraction per
+ * component (a list number outside 0 .. nlist-1: VLQ_ERR_INVALID, found by a device flag).  Synchronise the stream. */
+int vlq_pqtrain_subsample(vlq_pqtrain_t h, int64_t n, const float* x, int64_t m, int64_t seed, float* out);
+int vlq_pqtrain_residuals(vlq_pqtrain_t h, int64_t n, const float* x, const int64_t* assign, int64_t nlist, const float* centroids, float* out);
+/* Introspection, speed only: the last train or assign as text,
+ *   "route=batched kernel=pq_assign_kernel rows=128 group=4 ngroups=4 cols=256 kq=1 stride=4 vec=1 lds=49152 grid=192x4 n=65536
+ *    update=kmeans_update_packed_kernel iters=25 nsplit=0 assign_ms=0.1 group_ms=0.2 update_ms=0.1 train_assign_ms=2.5"
+ * (rows: the row tile; group / ngroups: slices per workgroup and groups per row; the times: stream time of the last iteration's
+ * assignment, grouping and update from events, and the sum of the assignments of the whole train).  Synchronises the stream. */
+int vlq_pqtrain_last_info(vlq_pqtrain_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,10 @@ SYMBOLS = [
     # k-means (vlq_kmeans_t)
     "vlq_kmeans_create", "vlq_kmeans_destroy", "vlq_kmeans_use_stream", "vlq_kmeans_set_params", "vlq_kmeans_set_centroids", "vlq_kmeans_train",
     "vlq_kmeans_get_centroids", "vlq_kmeans_objective", "vlq_kmeans_assign", "vlq_kmeans_update", "vlq_kmeans_last_info",
+    # product-quantizer training (vlq_pqtrain_t)
+    "vlq_pqtrain_create", "vlq_pqtrain_destroy", "vlq_pqtrain_use_stream", "vlq_pqtrain_set_params", "vlq_pqtrain_set_train_type",
+    "vlq_pqtrain_set_centroids", "vlq_pqtrain_get_centroids", "vlq_pqtrain_train", "vlq_pqtrain_objective", "vlq_pqtrain_assign",
+    "vlq_pqtrain_subsample", "vlq_pqtrain_residuals", "vlq_pqtrain_last_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -134,6 +138,7 @@ def lib():
         L.vlq_lsh_destroy.restype = None
         L.vlq_transform_destroy.restype = None
         L.vlq_kmeans_destroy.restype = None
+        L.vlq_pqtrain_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -176,6 +176,22 @@ __global__ __launch_bounds__(256) void kmeans_objective_end_kernel(const double*
     if (threadIdx.x == 0) status->obj = s;
 }
 
+// the same two trees over each of M contiguous rows of n distances (pq_train_api.hip: a slice's objective is kmeans_objective's bits)
+__global__ __launch_bounds__(256) void kmeans_objective_batch_kernel(const float* __restrict__ dis, int64_t n, double* __restrict__ partial) {
+    __shared__ double sh[256];
+    const float* row = dis + (size_t)blockIdx.y * n;
+    double s = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)kObjBlocks * 256) s += (double)row[i];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * kObjBlocks + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void kmeans_objective_batch_end_kernel(const double* __restrict__ partial, double* __restrict__ obj) {
+    __shared__ double sh[256];
+    const double s = block_sum((int)threadIdx.x < kObjBlocks ? partial[(size_t)blockIdx.x * kObjBlocks + threadIdx.x] : 0.0, sh);
+    if (threadIdx.x == 0) obj[blockIdx.x] = s;
+}
+
 __global__ __launch_bounds__(256) void kmeans_finite_kernel(const float* __restrict__ x, int64_t total, KMeansStatus* status) {
     const int64_t step = (int64_t)gridDim.x * 256;
     bool bad = false;
@@ -234,6 +250,11 @@ void launch_kmeans_renorm(float* c, int64_t k, int d, hipStream_t stream) {
 void launch_kmeans_objective(const float* dis, int64_t n, double* partial, KMeansStatus* status, hipStream_t stream) {
     hipLaunchKernelGGL(kmeans_objective_kernel, dim3(kObjBlocks), dim3(256), 0, stream, dis, n, partial);
     hipLaunchKernelGGL(kmeans_objective_end_kernel, dim3(1), dim3(256), 0, stream, partial, status);
+}
+
+void launch_kmeans_objective_batch(const float* dis, int64_t n, int M, double* partial, double* obj, hipStream_t stream) {
+    hipLaunchKernelGGL(kmeans_objective_batch_kernel, dim3(kObjBlocks, (unsigned)M), dim3(256), 0, stream, dis, n, partial);
+    hipLaunchKernelGGL(kmeans_objective_batch_end_kernel, dim3((unsigned)M), dim3(256), 0, stream, partial, obj);
 }
 
 void launch_kmeans_finite(const float* x, int64_t total, KMeansStatus* status, hipStream_t stream) {

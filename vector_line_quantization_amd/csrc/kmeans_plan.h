@@ -78,6 +78,8 @@ void launch_kmeans_split(float* cent, int d, const int* pairs, int nsplit, hipSt
 void launch_kmeans_gather(const float* x, const int* perm, int64_t m, int d, float* out, hipStream_t stream);       // out[i] = x[perm[i]]
 void launch_kmeans_renorm(float* c, int64_t k, int d, hipStream_t stream);       // fvec_renorm_L2 in place
 void launch_kmeans_objective(const float* dis, int64_t n, double* partial /* [kObjBlocks] */, KMeansStatus* status, hipStream_t stream);
+// obj[m] = that sum over dis[m][0 .. n), m < M (partial: [M][kObjBlocks])
+void launch_kmeans_objective_batch(const float* dis, int64_t n, int M, double* partial, double* obj, hipStream_t stream);
 void launch_kmeans_finite(const float* x, int64_t total, KMeansStatus* status, hipStream_t stream);
 void launch_kmeans_clear(KMeansStatus* status, hipStream_t stream);
 

@@ -90,6 +90,37 @@ class GpuIVFPQ:
     def set_search_options(self, by_residual=True, use_precomputed_table=1, max_codes=0):
         check(lib().vlq_ivfpq_set_search_options(self._h, C.c_int(int(by_residual)),
                                                  C.c_int(use_precomputed_table), C.c_int64(max_codes)))
+        self._by_residual = bool(by_residual)
+
+    def train(self, x, coarse=None, **kw):
+        """IndexIVFPQ::train for a flat coarse quantizer: the coarse centroids [nlist][d] by kmeans(x, nlist) unless given, then
+        train_residual_o (IndexIVFPQ.cpp:73-131) -- the subsample to max_points_per_centroid * ksub rows by rand_perm(n, seed), with
+        by_residual the residuals to the nearest coarse centroid (GpuFlat.search(., 1)), the PQ training on the device -- and both
+        are installed.  kw: the ClusteringParameters of the PQ training (GpuPQTrainer).  The rows stay on the device between the
+        steps.  Not built: a multi-index coarse quantizer, IVFPQR's second-level residuals, polysemous training."""
+        if not (_is_torch(x) and x.is_cuda):
+            import torch
+            x = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to("cuda:%d" % self.device)
+        if coarse is None:
+            coarse = kmeans(x, self.nlist, device=self.device)
+        tr = GpuPQTrainer(self.d, self.M, self.nbits, device=self.device, **kw)
+        try:
+            m = kw.get("max_points_per_centroid", 256) * self.ksub
+            xs = tr.subsample(x, m, kw.get("seed", 1234)) if x.shape[0] > m else x
+            if getattr(self, "_by_residual", True):
+                flat = GpuFlat(self.d, device=self.device)
+                try:
+                    flat.add(coarse)
+                    assign = flat.search(xs, 1)[1].reshape(-1)
+                finally:
+                    flat.close()
+                xs = tr.residuals(xs, assign, coarse)
+            pq = tr.train(xs)
+        finally:
+            tr.close()
+        self.set_coarse_centroids(coarse)
+        self.set_pq_centroids(pq)
+        return self
 
     @property
     def metric(self):
@@ -714,6 +745,11 @@ class GpuPQ(_GpuOneList):
         """ProductQuantizer::centroids [M][ksub][dsub]"""
         p, _k = _ptr(c, np.float32)
         self._call("set_centroids", p)
+
+    def train(self, x, **kw):
+        """IndexPQ::train without the polysemous training: ProductQuantizer::train on the device (train_pq), then set_centroids"""
+        self.set_centroids(train_pq(x, self.M, self.nbits, device=self.device, **kw))
+        return self
 
     def set_codes(self, codes):
         """IndexPQ::codes [ntotal][M] uint8; replaces the stored codes"""
@@ -1460,6 +1496,113 @@ def kmeans(x, k, **kw):
         return km.train(x)
     finally:
         km.close()
+
+
+class GpuPQTrainer:
+    """faiss::ProductQuantizer::train (ProductQuantizer.cpp:236-308) on the device (include/vlq_ivfpq.h, vlq_pqtrain_*): the
+    codebook [M][ksub][dsub] by M k-means runs over the column slices, batched -- one assignment launch per iteration scores
+    every row's M slices in place.  For every m the codebook and the objectives are those of
+    GpuKMeans(dsub, ksub, same parameters).train(x[:, m * dsub:(m + 1) * dsub]), bit for bit.  train_type: "default", "hot_start"
+    (the current codebook is the initialisation), "shared" (one k-means over all slices); the hypercube types raise."""
+
+    TRAIN_TYPES = {"default": 0, "hot_start": 1, "shared": 2, "hypercube": 3, "hypercube_pca": 4}      # ProductQuantizer::train_type_t
+    _PREFIX = "vlq_pqtrain_"
+    _call = _GpuOneList._call
+    close = _GpuOneList.close
+    __del__ = _GpuOneList.__del__
+    _out = GpuIVFPQ._out
+    _rows = GpuKMeans._rows
+    last_info = GpuKMeans.last_info
+
+    def __init__(self, d, M, nbits, niter=25, nredo=1, spherical=False, max_points_per_centroid=256, seed=1234, train_type="default", device=0):
+        self.d, self.M, self.nbits, self.device = d, M, nbits, device
+        self.ksub, self.dsub = 1 << nbits, d // M
+        self._h = C.c_void_p()
+        check(lib().vlq_pqtrain_create(C.byref(self._h), C.c_int(device), C.c_int(d), C.c_int(M), C.c_int(nbits)))
+        self._call("set_params", C.c_int(niter), C.c_int(nredo), C.c_int(int(spherical)), C.c_int64(max_points_per_centroid), C.c_int64(seed))
+        self.train_type = train_type
+
+    @property
+    def train_type(self):
+        return self._train_type
+
+    @train_type.setter
+    def train_type(self, t):
+        if t not in self.TRAIN_TYPES:
+            raise ValueError("train_type %r (one of %s)" % (t, sorted(self.TRAIN_TYPES)))
+        self._call("set_train_type", C.c_int(self.TRAIN_TYPES[t]))
+        self._train_type = t
+
+    def set_stream(self, stream_ptr):
+        self._call("use_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_centroids(self, c):
+        if tuple(c.shape) != (self.M, self.ksub, self.dsub):
+            raise ValueError("centroids must be [M=%d][ksub=%d][dsub=%d]" % (self.M, self.ksub, self.dsub))
+        self._call("set_centroids", _ptr(c, np.float32)[0])
+
+    def train(self, x, init=None):
+        """ProductQuantizer::train: the codebook [M][ksub][dsub] (on x's device).  init: a codebook to start this call from"""
+        n, (px, _a) = self._rows(x)
+        if init is not None:
+            self.set_centroids(init)
+            self._call("set_train_type", C.c_int(self.TRAIN_TYPES["hot_start"]))
+        try:
+            self._call("train", C.c_int64(n), px)
+        finally:
+            self._call("set_train_type", C.c_int(self.TRAIN_TYPES[self._train_type]))
+        self._like = x
+        return self.centroids
+
+    @property
+    def centroids(self):
+        out = self._out(None, (self.M, self.ksub, self.dsub), np.float32, getattr(self, "_like", None))
+        self._call("get_centroids", _out_ptr(out, np.float32)[0])
+        return out
+
+    @property
+    def obj(self):
+        """[M][niter * nredo]: every slice's objective in front of every update of the last train"""
+        cnt = C.c_int(0)
+        self._call("objective", None, C.c_int(0), C.byref(cnt))
+        out = np.empty((cnt.value,), np.float64)
+        self._call("objective", out.ctypes.data_as(C.c_void_p), C.c_int(cnt.value), C.byref(cnt))
+        return out.reshape(self.M, -1)
+
+    def assign(self, x):
+        """(D [M][n], I [n][M]): the squared distance to and the label m * ksub + c of the nearest centroid of every slice"""
+        n, (px, _a) = self._rows(x)
+        D = self._out(None, (self.M, n), np.float32, x)
+        I = self._out(None, (n, self.M), np.int64, x)
+        self._call("assign", C.c_int64(n), px, _out_ptr(D, np.float32)[0], _out_ptr(I, np.int64)[0])
+        return D, I
+
+    def subsample(self, x, m, seed=1234):
+        """x[rand_perm(n, seed)[:m]]"""
+        n, (px, _a) = self._rows(x)
+        out = self._out(None, (m, self.d), np.float32, x)
+        self._call("subsample", C.c_int64(n), px, C.c_int64(m), C.c_int64(seed), _out_ptr(out, np.float32)[0])
+        return out
+
+    def residuals(self, x, assign, centroids):
+        """x - centroids[assign] in float32"""
+        n, (px, _a) = self._rows(x)
+        if tuple(assign.shape) != (n,) or centroids.ndim != 2 or centroids.shape[1] != self.d:
+            raise ValueError("assign must be [n=%d], centroids [nlist][d=%d]" % (n, self.d))
+        pa, _b = _ptr(assign, np.int64)
+        pc, _c = _ptr(centroids, np.float32)
+        out = self._out(None, (n, self.d), np.float32, x)
+        self._call("residuals", C.c_int64(n), px, pa, C.c_int64(centroids.shape[0]), pc, _out_ptr(out, np.float32)[0])
+        return out
+
+
+def train_pq(x, M, nbits, **kw):
+    """The codebook [M][ksub][dsub] of GpuPQTrainer(d, M, nbits, **kw).train(x)"""
+    tr = GpuPQTrainer(x.shape[1], M, nbits, **kw)
+    try:
+        return tr.train(x)
+    finally:
+        tr.close()
 
 
 class GpuVLQ:
