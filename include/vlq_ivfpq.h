@@ -968,6 +968,45 @@ int vlq_pqtrain_residuals(vlq_pqtrain_t h, int64_t n, const float* x, const int6
  * assignment, grouping and update from events, and the sum of the assignments of the whole train).  Synchronises the stream. */
 int vlq_pqtrain_last_info(vlq_pqtrain_t h, char* buf, int cap);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Moments of a training set: the column means and the centred second-moment matrix, the two passes PCAMatrix::train
+ * (VectorTransform.cpp:316-456) spends its time in, on the device (csrc/moments.hip, csrc/moments_plan.h).
+ * One handle is one shape: rows of dx floats, and of dy floats for a second operand (dy = 0: the symmetric case, y with itself).
+ *   mean[j] = (sum over i of x[i][j]) / n: fp32 sums over row slices of a fixed length, the slices' sums added in ascending order
+ *     in double, one division.
+ *   C[a][b] = sum over i of xc[i][a] * yc[i][b], [dx][dy] row-major (symmetric: [dx][dx]), NOT divided by anything (as the
+ *     reference's ssyrk_ result is not).  With center, xc[i][a] = x[i][a] - mean_x[a] rounded to fp32 (one subtraction per
+ *     component) and the same for y; without, the operands themselves.  This is the covariance of the centred rows, not the
+ *     reference's X^T X - n mean mean^T, which cancels in fp32 for data far from the origin.  The products are summed in fp32 on
+ *     the matrix units within a row slice; the slices' partials are added in ascending order in double and rounded once.
+ *     Symmetric: C[a][b] and C[b][a] are written from one value, C == C^T bit for bit.
+ *   Nothing is atomic: for device rows the bits depend on (n, dx, dy) only; host rows are staged in pages of 32 768 under the plan
+ *   of one page, every page adding onto the partials of the pages before it, so host rows give bits of their own (equally fixed).
+ *   The summation order is this library's, as the reference's is its BLAS's: the two agree within the rounding bound of an fp32
+ *   dot product of n terms, not bit for bit.
+ * Limits: 1 <= dx, dy <= VLQ_TRANSFORM_MAX_D (VLQ_ERR_UNSUPPORTED beyond), 1 <= n < 2^31.  Pointers [h|d]. */
+typedef struct vlq_moments_s* vlq_moments_t;
+
+/* dy = 0: symmetric, every later call's y and mean_y must be NULL */
+int vlq_moments_create(vlq_moments_t* out, int device, int dx, int dy);
+void vlq_moments_destroy(vlq_moments_t h);
+/* the stream compute issues its work on (synchronises the old one first); not named set_stream, as vlq_kmeans_use_stream is not:
+ * the handle is no index and has no stream-ordered search contract */
+int vlq_moments_use_stream(vlq_moments_t h, void* hip_stream);
+/* Speed only, for timing the plan's alternatives: kr = rows of a staged strip (16, 32, 64), slices = row slices S of a launch;
+ * 0 = the plan decides.  Another split is another summation order: results move within the bound above. */
+int vlq_moments_set_split(vlq_moments_t h, int kr, int slices);
+/* x[n*dx], y[n*dy] or NULL (symmetric) -> mean_x[dx] or NULL, mean_y[dy] or NULL, C[dx*dy].  center != 0: the means are
+ * subtracted; 0: they are only reported (where asked for).  Device outputs are written on the handle's stream without
+ * synchronising; with any output in host memory the call synchronises the stream and all outputs are there on return. */
+int vlq_moments_compute(vlq_moments_t h, int64_t n, const float* x, const float* y, int center, float* mean_x, float* mean_y, float* C);
+/* Introspection, speed only: the plan of the last compute as text (before any: the plan of 32 768 rows),
+ *   "kernel=moment_kernel pairs=3 S=169 slice_len=416 kr=32 lds=65536 scratch=33226752 col_slices=274 col_slice_len=256 n=70001
+ *    pages=1 moment_ms=0.1"
+ * (pairs: output tiles of 128 x 128; S, slice_len: row slices of a launch and their length; lds, scratch: bytes; moment_ms: the
+ * stream time of the call's moment_kernel launches, staging copies of host pages included, from events).  Synchronises the stream. */
+int vlq_moments_last_info(vlq_moments_t h, char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

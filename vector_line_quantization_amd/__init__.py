@@ -6,7 +6,7 @@ bench.py and the multi-GPU driver.  There is no CPU implementation in here: if
 the library is missing or no HIP device is present, calls fail loudly.
 """
 from ._lib import VlqError, build_library, device_count, lib, library_path  # noqa: F401
-from .index import (GpuFlat, GpuIVFFlat, GpuIVFPQ, GpuIVFSQ, GpuKMeans, GpuLinearTransform, GpuLSH, GpuNormalization, GpuPQ, GpuPQTrainer, GpuPreTransform,  # noqa: F401
-                    GpuRefineFlat, GpuRemapDimensions, GpuSQ, GpuVLQ, kmeans, random_rotation, train_pq)
+from .index import (GpuFlat, GpuIVFFlat, GpuIVFPQ, GpuIVFSQ, GpuKMeans, GpuLinearTransform, GpuLSH, GpuMoments, GpuNormalization, GpuPQ, GpuPQTrainer, GpuPreTransform,  # noqa: F401
+                    GpuRefineFlat, GpuRemapDimensions, GpuSQ, GpuVLQ, kmeans, random_rotation, train_pca, train_pq)
 
-__all__ = ["GpuFlat", "GpuIVFFlat", "GpuIVFPQ", "GpuIVFSQ", "GpuKMeans", "GpuLinearTransform", "GpuLSH", "GpuNormalization", "GpuPQ", "GpuPQTrainer", "GpuPreTransform", "GpuRefineFlat", "GpuRemapDimensions", "GpuSQ", "GpuVLQ", "VlqError", "build_library", "device_count", "kmeans", "lib", "library_path", "random_rotation", "train_pq"]
+__all__ = ["GpuFlat", "GpuIVFFlat", "GpuIVFPQ", "GpuIVFSQ", "GpuKMeans", "GpuLinearTransform", "GpuLSH", "GpuMoments", "GpuNormalization", "GpuPQ", "GpuPQTrainer", "GpuPreTransform", "GpuRefineFlat", "GpuRemapDimensions", "GpuSQ", "GpuVLQ", "VlqError", "build_library", "device_count", "kmeans", "lib", "library_path", "random_rotation", "train_pca", "train_pq"]

@@ -61,6 +61,8 @@ SYMBOLS = [
     "vlq_pqtrain_create", "vlq_pqtrain_destroy", "vlq_pqtrain_use_stream", "vlq_pqtrain_set_params", "vlq_pqtrain_set_train_type",
     "vlq_pqtrain_set_centroids", "vlq_pqtrain_get_centroids", "vlq_pqtrain_train", "vlq_pqtrain_objective", "vlq_pqtrain_assign",
     "vlq_pqtrain_subsample", "vlq_pqtrain_residuals", "vlq_pqtrain_last_info",
+    # column means and the centred second-moment matrix (vlq_moments_t)
+    "vlq_moments_create", "vlq_moments_destroy", "vlq_moments_use_stream", "vlq_moments_set_split", "vlq_moments_compute", "vlq_moments_last_info",
     # include/vlq_line.h
     "vlq_line_set_float16_tables", "vlq_line_set_row_mode", "vlq_line_set_scan_parts", "vlq_line_create", "vlq_line_destroy", "vlq_line_set_stream", "vlq_line_set_coarse_centroids",
     "vlq_line_set_pq_centroids", "vlq_line_set_lambda_codebook", "vlq_line_set_graph",
@@ -139,6 +141,7 @@ def lib():
         L.vlq_transform_destroy.restype = None
         L.vlq_kmeans_destroy.restype = None
         L.vlq_pqtrain_destroy.restype = None
+        L.vlq_moments_destroy.restype = None
         L.vlq_line_ntotal.restype = C.c_int64
         L.vlq_line_destroy.restype = None
         _lib = L

@@ -1605,6 +1605,126 @@ def train_pq(x, M, nbits, **kw):
         tr.close()
 
 
+class GpuMoments:
+    """Column means and the centred second-moment matrix of a training set on the device (include/vlq_ivfpq.h, vlq_moments_*):
+    C = (x - mean_x)^T (y - mean_y), [dx][dy], divided by nothing; dy = 0 is the symmetric case C = xc^T xc, [dx][dx] and exactly
+    symmetric.  The two passes PCAMatrix::train spends its time in; the second operand is the OPQ loop's x^T * pq_recons.
+    Rows may be numpy arrays or torch tensors; outputs follow x's device (device outputs are written on the handle's stream
+    without synchronising, host outputs are complete on return)."""
+
+    _PREFIX = "vlq_moments_"
+    _call = _GpuOneList._call
+    close = _GpuOneList.close
+    __del__ = _GpuOneList.__del__
+    _out = GpuIVFPQ._out
+    last_info = GpuKMeans.last_info
+
+    def __init__(self, dx, dy=0, device=0):
+        self.dx, self.dy, self.device = dx, dy, device
+        self._h = C.c_void_p()
+        check(lib().vlq_moments_create(C.byref(self._h), C.c_int(device), C.c_int(dx), C.c_int(dy)))
+
+    def set_stream(self, stream_ptr):
+        self._call("use_stream", C.c_void_p(stream_ptr or 0))
+
+    def set_split(self, kr=0, slices=0):
+        """speed only (timing the plan's alternatives): rows of a staged strip (16, 32, 64) and row slices; 0 = the plan decides"""
+        self._call("set_split", C.c_int(kr), C.c_int(slices))
+
+    def compute(self, x, y=None, center=True):
+        """(mean_x [dx], mean_y [dy] or None, C [dx][dy or dx]).  center=False: the means are reported but not subtracted"""
+        if x.ndim != 2 or x.shape[1] != self.dx:
+            raise ValueError("rows of %d floats expected, got shape %s" % (self.dx, tuple(x.shape)))
+        if (y is None) != (self.dy == 0):
+            raise ValueError("dy=%d: a second operand is %s" % (self.dy, "not taken" if self.dy == 0 else "needed"))
+        n = x.shape[0]
+        if y is not None and tuple(y.shape) != (n, self.dy):
+            raise ValueError("y must be [n=%d][dy=%d], got shape %s" % (n, self.dy, tuple(y.shape)))
+        px, _a = _ptr(x, np.float32)
+        py, _b = _ptr(y, np.float32)
+        mean_x = self._out(None, (self.dx,), np.float32, x)
+        mean_y = None if y is None else self._out(None, (self.dy,), np.float32, x)
+        Cm = self._out(None, (self.dx, self.dy or self.dx), np.float32, x)
+        self._call("compute", C.c_int64(n), px, py, C.c_int(int(center)), _out_ptr(mean_x, np.float32)[0],
+                   None if y is None else _out_ptr(mean_y, np.float32)[0], _out_ptr(Cm, np.float32)[0])
+        return mean_x, mean_y, Cm
+
+
+_random_rotation = random_rotation           # train_pca has a parameter of that name
+
+
+def train_pca(x, d_out, eigen_power=0.0, random_rotation=False, balanced_bins=0, have_bias=True, max_points_per_d=1000, seed=1234, device=0):
+    """faiss::PCAMatrix::train followed by prepare_Ab (VectorTransform.cpp:316-565): a GpuLinearTransform(d_in, d_out, A, b) that
+    also carries .A, .b, .mean [d_in], .eigenvalues [d_in] (descending) and .PCAMat [d_in][d_in] (eigenvectors as rows) as numpy arrays;
+    it goes straight into GpuPreTransform([pca], base).
+      1. more than max_points_per_d * d_in rows are subsampled to x[rand_perm(n, seed)[:that many]] (fvecs_maybe_subsample);
+      2. the mean and the second-moment matrix of the rows by GpuMoments on the device (have_bias=False: the mean is zero and
+         nothing is subtracted);
+      3. the d_in x d_in matrix is decomposed in float64 by numpy.linalg.eigh (the reference's dsyev_);
+      4. prepare_Ab in numpy: the first d_out eigenvectors, rows scaled by eigenvalue ** eigen_power; balanced_bins: the greedy
+         assignment of the rows to bins of equal eigenvalue mass; random_rotation: A = R diag(factors) PCAMat[:d_out] with
+         R = random_rotation(d_out, d_out, seed=5) (a random rotation, not the bits of the reference's); b = -A mean.
+    Differences from the reference, on purpose: the matrix is the covariance of the CENTRED rows (one fp32 subtraction per
+    component as the rows are staged), not X^T X - n mean mean^T, which cancels catastrophically in fp32 for data far from the
+    origin; like the reference's it is divided by nothing, so the eigenvalues are sums, not variances.  Neither is bit-reproducible
+    against the other: the summation order is this library's there and a BLAS's in the reference; both obey the rounding bound of
+    an fp32 dot product of n terms.  n < d_in (the reference's Gram-matrix branch) is not built and raises ValueError."""
+    import torch
+    if x.ndim != 2:
+        raise ValueError("rows expected, got shape %s" % (tuple(x.shape),))
+    n, d_in = x.shape
+    if n < d_in:
+        raise ValueError("train_pca needs at least d_in=%d rows, got %d (the Gram-matrix route for fewer rows is not built)" % (d_in, n))
+    if not 1 <= d_out <= d_in:
+        raise ValueError("PCA matrix cannot output %d dimensions from %d" % (d_out, d_in))
+    if balanced_bins and (random_rotation or d_out % balanced_bins):
+        raise ValueError("balanced_bins must divide d_out and excludes random_rotation")
+    dev = torch.device("cuda", device)
+    if not (_is_torch(x) and x.is_cuda):
+        x = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+    torch.cuda.synchronize(dev)                # the handles below work on streams of their own
+    m = max_points_per_d * d_in
+    if n > m:
+        sub = GpuPQTrainer(d_in, 1, 1, device=device)
+        try:
+            x = sub.subsample(x, m, seed)
+            sub.last_info()                    # (synchronises the trainer's stream: the rows are there)
+        finally:
+            sub.close()
+    mom = GpuMoments(d_in, device=device)
+    try:
+        mean, _none, cov = mom.compute(x, center=have_bias)
+        mom.last_info()                        # (synchronises the handle's stream: the device outputs are there)
+        cov = cov.cpu().numpy().astype(np.float64)
+        mean = mean.cpu().numpy() if have_bias else np.zeros(d_in, np.float32)
+    finally:
+        mom.close()
+    w, v = np.linalg.eigh(cov)                 # ascending; columns are the eigenvectors
+    eigenvalues = np.ascontiguousarray(w[::-1], dtype=np.float32)
+    pcamat = np.ascontiguousarray(v[:, ::-1].T, dtype=np.float32)
+    factors = np.power(eigenvalues[:d_out], np.float32(eigen_power)).astype(np.float32) if eigen_power != 0 else np.ones(d_out, np.float32)
+    if not random_rotation:
+        A = pcamat[:d_out] * factors[:, None]
+        if balanced_bins:
+            dsub, Ain = d_out // balanced_bins, A
+            A = np.empty_like(Ain)
+            accu, counter = np.zeros(balanced_bins, np.float32), np.zeros(balanced_bins, np.int64)
+            for i in range(d_out):             # greedy: the lightest bin that still has room, the first of equals
+                open_bins = np.where(counter < dsub)[0]
+                j = open_bins[np.argmin(accu[open_bins])]
+                A[j * dsub + counter[j]] = Ain[i]
+                accu[j] += eigenvalues[i]
+                counter[j] += 1
+    else:
+        rr = _random_rotation(d_out, d_out, seed=5)
+        A = ((rr * factors[None, :]).astype(np.float64) @ pcamat[:d_out].astype(np.float64)).astype(np.float32)
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    b = (-(A.astype(np.float64) @ mean.astype(np.float64))).astype(np.float32)
+    pca = GpuLinearTransform(d_in, d_out, A, b, is_orthonormal=(eigen_power == 0), device=device)
+    pca.A, pca.b, pca.mean, pca.eigenvalues, pca.PCAMat = A, b, mean, eigenvalues, pcamat
+    return pca
+
+
 class GpuVLQ:
     """The fork's vector-and-line-quantization index (include/vlq_line.h):
     GpuIndexIVFPQ(resources, dims, nlist, M, nbits, nedge, nLambda, ...) of
